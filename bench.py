@@ -7,10 +7,12 @@ One "step" = one mini-batch through the whole path, inputs resident in HBM when 
 Workload (BASELINE.json metric): papers100M-shaped graph (N=111 059 956, E=1 615 685 872, D=128 f32), GraphSAGE fanout
 [25,10], batch 8000.  The graph is the R-MAT graph of SURVEY.md 8(d) (fgnn_hip/rmat.py; --graph powerlaw = round 1's).
 
---gpus 1   one GPU does both halves through the kernel-level C ABI (libfgnn_hip.so), full feature table in HBM; after
-           the timed region two more are measured and reported beside it: the sampler-side stage alone, and BASELINE
-           config 3's extract leg (features in host memory, HBM cache of the top cache_ratio*N rows ranked by the
-           pre-sampler, misses gathered over the host link).
+--gpus 1   one GPU does both halves through the kernel-level C ABI (libfgnn_hip.so), full feature table in HBM.  A plain
+           run sets up, warms up, times --windows windows of --steps steps each and prints the line.  With --full more
+           is measured after the timed region and reported beside it: the sampler-side stage alone, BASELINE config 3's
+           extract leg (features in host memory, HBM cache of the top cache_ratio*N rows ranked by the pre-sampler,
+           misses gathered over the host link), the training leg, the CPU baselines.  --dump-outputs DIR writes the
+           last timed step's batch as .npy files (same arguments: same inputs, same batch).
 --gpus N   the factored pipeline of the reference (multi_gpu/train_graphsage.py:103-432): S sampler processes and
            N - S trainer processes, one per GPU, driving arch5 through samgraph.torch / c_lib.so -- DistShuffler step
            ranges per sampler (dist_shuffler.cc:59-79), hand-off through the HBM message ring, trainers extracting
@@ -89,6 +91,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=151)   # one papers100M epoch at batch 8000
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: N=1 the random-read probe, the sampler-side "
+                         "stage, the serial gather, config 3's extract leg, the training leg, the device-copy reference "
+                         "and the CPU baselines; N>=2 the training span and the like-for-like N = 1 point.  Without it "
+                         "a run sets up, warms up, times the windows and prints the line (those fields are null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N=1: after the timed windows write what the LAST timed step's batch holds (graph layers, input "
+                         "/ output nodes, cache-index arrays, features, labels) as DIR/<name>.npy, float64 (features "
+                         "float32); arrays beyond their share of 64 MB as a fixed seeded sample of rows")
     ap.add_argument("--windows", type=int, default=5,
                     help="timed windows of --steps steps each, back to back; `value` is the median window's")
     ap.add_argument("--workload", default=os.environ.get("FGNN_BENCH_WORKLOAD", "papers100M"), choices=list(WORKLOADS))

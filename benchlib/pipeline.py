@@ -356,7 +356,8 @@ def run_pipeline_rank(args, rank, world):
     child_env = {k: v for k, v in os.environ.items()
                  if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                               "TORCHELASTIC_RUN_ID", "FGNN_BENCH_CHILD")}
-    if rank == 0 and not (args.rehearse or args.no_n1_point or args.decoupled):
+    full = bool(getattr(args, "full", False))  # a plain run: the span behind the headline only
+    if rank == 0 and full and not (args.rehearse or args.no_n1_point or args.decoupled):
         # started now, before this process touches the GPU; it sleeps on its stdin until the spans are done
         # FGNN_BENCH_N1_WRAP (tools): a profiler in front of the child, e.g. "rocprofv3 --kernel-trace --stats -d DIR --"
         wrap = os.environ.get("FGNN_BENCH_N1_WRAP", "").split()
@@ -423,7 +424,7 @@ def run_pipeline_rank(args, rank, world):
     R = 1 if args.decoupled else max(1, args.windows)
     T_ = T
     lead, tail = span_margins(W, T_, args.decoupled)
-    K2 = 0 if (args.no_train_leg or args.rehearse) else train_region_batches(K, args.train_steps, T_)[1]
+    K2 = 0 if (args.no_train_leg or args.rehearse or not full) else train_region_batches(K, args.train_steps, T_)[1]
     total1 = span_total(lead, R, K, tail, T_, False)
     total2 = span_total(lead, R, K2, tail, T_, True) if K2 else 0
     try:

@@ -28,6 +28,9 @@ def run_single(args):
         w = dict(w, num_walks=args.num_walks)
     if args.sample_type is None:
         args.sample_type = w["sample_type"]
+    # a plain run measures the headline only; --full adds the measurements that take runs of their own
+    full = bool(getattr(args, "full", False))
+    extras = full and not args.timed_only
     t_setup = time.time()
     indptr, indices, num_edge, graph_desc = gen_graph(args, w, dev)
     feat = gen_features_on_gpu(w["num_node"], w["feat_dim"], dev)
@@ -192,10 +195,11 @@ def run_single(args):
     # what the memory system sustains for the sampling chain's access pattern HERE and NOW: independent random 4-byte
     # reads from the CSR (6.5 GB: far beyond every cache), ~20 ms, nothing else on the GPU (roofline_sample's ceiling)
     probe_reads_per_s = None
-    try:
-        probe_reads_per_s = lib.random_read_rate(indices)
-    except Exception:
-        pass
+    if full:
+        try:
+            probe_reads_per_s = lib.random_read_rate(indices)
+        except Exception:
+            pass
     # R timed windows of EXACTLY args.steps steps each, back to back (a 151-step window is ~20 ms: one window is a thin
     # basis for a headline); every window is bracketed by a device synchronise on both sides, all R values are
     # published and `value` is the MEDIAN window's
@@ -223,13 +227,16 @@ def run_single(args):
     del windows
 
     next_seq = prime + args.warmup + R * args.steps  # sequence numbers must stay consecutive
+    if getattr(args, "dump_outputs", None):
+        # the batch of the last timed step still sits in its buffer (nothing has reused it yet)
+        dump_batch(args.dump_outputs, batches[(next_seq - 1) % NBUF])
     metas_t, gather_t = list(metas), list(gather_ms)
     # the sampler-side stage alone (what the reference's kLogEpochSampleTotalTime covers: shuffle slice + sample +
     # dedup + remap + cache-index split, dist_loops_arch5.cc:98-105), same overlap, no feature gather
     metas.clear()
     gather_ms.clear()
     sample_stage = None
-    if not args.timed_only:
+    if extras:
         mode[0] = "sample"
         # two batch streams: without the gather the stage is bound by khop2's order chain and a third batch in flight only
         # slows the chain's kernels (0.071 ms per batch against 0.076 with three; an arch5 sampler process, which also
@@ -282,7 +289,7 @@ def run_single(args):
     # the gather with nothing else on the GPU (one thread, one stream): separates the kernel's own efficiency from
     # the slowdown it accepts when it shares the chip with the next batch's sampling chain
     serial = None
-    if (NT > 1 or SPT > 1) and not args.timed_only:
+    if (NT > 1 or SPT > 1) and extras:
         nt_saved, spt_saved = NT, SPT
         NT = SPT = 1
         with no_gc():
@@ -303,7 +310,7 @@ def run_single(args):
     # rows ranked by the pre-sampler (dist/pre_sampler.cc:75-162 -> fgnn_presample_count / fgnn_presample_rank), hit
     # rows from the cache, miss rows read by the gather kernel over the host link (dist_loops.cc:713-846)
     extract_leg = None
-    if args.cache_ratio > 0 and not args.timed_only and not args.no_extract_leg and args.sample_type in ("khop2", "khop0"):
+    if args.cache_ratio > 0 and extras and not args.no_extract_leg and args.sample_type in ("khop2", "khop0"):
         try:
             extract_leg, next_seq = run_extract_leg(args, w, dev, sampler, batches, streams, train, feat, label,
                                                     steps_per_epoch, next_seq, run_region, timed_region, mode, leg, metas,
@@ -314,7 +321,7 @@ def run_single(args):
     # next batch's sample + extract chain runs on a side stream under the current batch's GraphSAGE step
     # (examples/models.py, hidden 256, fused Adam), like the reference's arch3 threads
     train_leg = None
-    if not args.timed_only and not args.no_train_leg and args.sample_type != "random_walk":
+    if extras and not args.no_train_leg and args.sample_type != "random_walk":
         try:
             train_leg, next_seq = run_train_leg(args, w, dev, sampler, batches, streams, seeds_of, table, feat, label,
                                                 steps_per_epoch, next_seq, mode)
@@ -342,20 +349,21 @@ def run_single(args):
     # reference point next to the 8 TB/s spec peak the fraction is quoted against: what torch's plain device-to-device
     # copy of 2 GiB reaches on this GPU right now (read + write bytes per second; ordinary loads/stores -- the gather's
     # non-temporal accesses beat it)
-    a = torch.empty(1 << 29, dtype=torch.float32, device=dev)
-    bdst = torch.empty_like(a)
-    bdst.copy_(a)
-    copies = []
-    for _ in range(5):  # five measurements of 4 copies each: the spread tells a noisy box from a slow one
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(4):
-            bdst.copy_(a)
-        e1.record()
-        torch.cuda.synchronize()
-        copies.append(4 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9)
-    copy_gbs = float(np.median(copies))
-    del a, bdst
+    copies, copy_gbs = [], None
+    if full:
+        a = torch.empty(1 << 29, dtype=torch.float32, device=dev)
+        bdst = torch.empty_like(a)
+        bdst.copy_(a)
+        for _ in range(5):  # five measurements of 4 copies each: the spread tells a noisy box from a slow one
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                bdst.copy_(a)
+            e1.record()
+            torch.cuda.synchronize()
+            copies.append(4 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9)
+        copy_gbs = float(np.median(copies))
+        del a, bdst
     out = {
         "metric": f"sampled-edges/sec ({args.sample_type} fanout {'/'.join(map(str, w['fanout']))}, batch {bs}, full hot "
                   f"path: sample + dedup + remap + cache-index split + feature/label gather; median of {R} timed windows "
@@ -393,7 +401,8 @@ def run_single(args):
                                "window (event records on every batch cost the step 3 %)",
                      "algorithmic_bytes_per_launch": gather_feat_bytes / len(metas),
                      "serial": serial, "torch_copy_GBps": copy_gbs,
-                     "torch_copy_GBps_spread": {"min": min(copies), "max": max(copies), "samples": copies}},
+                     "torch_copy_GBps_spread": ({"min": min(copies), "max": max(copies), "samples": copies}
+                                                if copies else None)},
         "roofline_extract": extract_leg,
         # the N >= 2 lines measure the factored pipeline with the features in HOST memory behind a cache_ratio cache; the
         # same work on ONE GPU (this process samples AND does the cached extraction with host misses) is the N = 1 point
@@ -425,7 +434,7 @@ def run_single(args):
         "overflow": bool(overflow), "setup_s": t_setup,
         "host_threads": NT, "streams": NT * SPT, "host_enqueue_ms_per_step": host_enqueue_ms,
     }
-    if not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         if args.sample_type in ("khop2", "khop0"):
             out["cpu_baseline"] = cpu_baseline(w, indptr, indices, feat, train, sample_type=args.sample_type)
         else:
@@ -447,6 +456,39 @@ def run_single(args):
                       "train_leg_ms_per_step": train_leg.get("ms_per_step") if train_leg else None,
                       "cpu_baseline_edges_per_s": (out.get("cpu_baseline") or {}).get("value")}
     print(json.dumps(out), flush=True)
+
+
+def dump_batch(out_dir, bt, budget=60 << 20, feat_share=24 << 20):
+    """--dump-outputs: what a caller of the timed path receives for one (waited-for) batch, as <out_dir>/<name>.npy --
+    per layer the COO arrays and (num_src, num_dst), input / output nodes, the four cache-index arrays, labels (float64:
+    every 32-bit id is exact) and the gathered features (float32).  An array beyond its share of the budget (64 MB in
+    all) is written as a sample of its rows: sorted indices drawn by a generator seeded with the array's length only,
+    so two builds given the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    m = bt.meta
+    ids = {}
+    for l in range(m.num_layers):
+        row, col, nsrc, ndst = bt.graph(l)
+        ids["layer%d_row" % l], ids["layer%d_col" % l] = row, col
+        ids["layer%d_num_src_dst" % l] = torch.tensor([nsrc, ndst], dtype=torch.int64)
+    ids["input_nodes"], ids["output_nodes"], ids["label"] = bt.input_nodes(), bt.output_nodes(), bt.label()
+    for name, t in zip(("miss_src_index", "miss_dst_index", "cache_src_index", "cache_dst_index"), bt.cache_index_arrays()):
+        ids[name] = t
+    share = (budget - feat_share) // len(ids)
+
+    def write(name, t, dtype, cap):
+        a = t.detach().cpu().numpy()
+        if a.dtype == np.int32:  # node ids and edge endpoints are unsigned 32-bit words
+            a = a.view(np.uint32)
+        rows = max(1, cap // max(1, (a[0].size if a.ndim > 1 and len(a) else 1) * np.dtype(dtype).itemsize))
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(len(a)).choice(len(a), size=rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    torch.cuda.synchronize()
+    for name, t in ids.items():
+        write(name, t, np.float64, share)
+    write("feat", bt.feat(), np.float32, feat_share)
 
 
 def run_extract_leg(args, w, dev, sampler, batches, streams, train, feat, label, steps_per_epoch, next_seq, run_region,

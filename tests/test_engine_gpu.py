@@ -331,7 +331,7 @@ def test_bench_pipeline_two_processes_weighted_and_walks(tmp_path, sample_type):
     as edge data, the trainers a PinSAGE) -- sampler process -> HBM ring -> trainer process, training span included."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "small",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--workload", "small",
                         "--sample-type", sample_type, "--steps", "10", "--warmup", "3", "--train-steps", "4",
                         "--no-n1-point", "--empty-feat-bits", "16"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=str(tmp_path))
@@ -349,8 +349,8 @@ def test_bench_pipeline_two_processes(tmp_path):
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "small", "--steps",
-                        "12", "--warmup", "3", "--train-steps", "4", "--empty-feat-bits", "16"], capture_output=True,
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--workload", "small",
+                        "--steps", "12", "--warmup", "3", "--train-steps", "4", "--empty-feat-bits", "16"], capture_output=True,
                        text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -383,8 +383,8 @@ def test_bench_pipeline_two_samplers_three_trainers(tmp_path):
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "5", "--samplers", "2", "--workload",
-                        "small", "--steps", "15", "--warmup", "6", "--train-steps", "6", "--empty-feat-bits", "16",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "5", "--full", "--samplers", "2",
+                        "--workload", "small", "--steps", "15", "--warmup", "6", "--train-steps", "6", "--empty-feat-bits", "16",
                         "--no-n1-point"],  # (its child would be the 7th process on this box's one GPU: the limit is 6)
                        capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]

@@ -18,38 +18,35 @@ def test_constants_match_reference(golden_dir):
     assert sc.cpu(1) == "cpu:1" and sc.gpu(3) == "cuda:3"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/example/samgraph"),
-                    reason="needs the reference tree (build container only)")
 @pytest.mark.parametrize("mode,argv", [
     ("NORMAL", []),                                          # defaults: arch3, khop0
     ("NORMAL", ["--arch", "arch2", "--sample-type", "khop2", "--cache-percentage", "0.1", "--pipeline"]),
     ("FGNN", ["--num-sample-worker", "2", "--num-train-worker", "3", "--cache-percentage", "0.2"]),
 ])
-def test_reference_common_config_is_accepted_unchanged(tmp_path, mode, argv):
-    """The reference's own CLI/config harness (example/samgraph/common_config.py, imported from where it lies) builds
-    the run_config dict with THIS repo's samgraph package behind `import samgraph.torch as sam`; samgraph_config must
-    take the dict as it is (keys, value formats, unknown keys ignored)."""
+def test_reference_common_config_is_accepted_unchanged(tmp_path, golden_dir, mode, argv):
+    """The run_config dict the reference's own CLI/config harness (example/samgraph/common_config.py) builds for these
+    arguments with THIS repo's samgraph package behind `import samgraph.torch as sam`, as recorded in
+    tests/golden/common_config_run_configs.json; samgraph_config must take the dict as it is (keys, value formats,
+    unknown keys ignored), and the enum values the harness looked up by name are this package's."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(golden_dir, "common_config_run_configs.json")) as f:
+        cases = json.load(f)["cases"]
+    rc = next(c["run_config"] for c in cases if c["mode"] == mode and c["argv"] == argv)
+    assert rc["fanout"] == [25, 10] and rc["num_fanout"] == rc["num_layer"] == 2
     code = r'''
-import sys, argparse
+import sys
 sys.path.insert(0, %r)
-sys.path.insert(0, "/root/reference/example/samgraph")
 import samgraph.torch as sam
-from common_config import RunMode, get_default_common_config, add_common_arguments, process_common_config
-rc = {}
-rc.update(get_default_common_config(run_mode=RunMode.%s))
-rc["fanout"] = [25, 10]
-ap = argparse.ArgumentParser()
-add_common_arguments(ap, rc)
-rc.update(vars(ap.parse_args(%r)))
-process_common_config(rc)
-rc["num_fanout"] = rc["num_layer"] = len(rc["fanout"])
+rc = %r
+assert rc["_arch"] == sam.builtin_archs[rc["arch"]]["arch"]
+assert rc["_sample_type"] == sam.sample_types[rc["sample_type"]]
+assert rc["_cache_policy"] == sam.cache_policies[rc["cache_policy"]]
 sam.config(rc)
 assert sam.num_epoch() == rc["num_epoch"]
 print("accepted", rc["_arch"], rc["_sample_type"], rc["num_epoch"])
-''' % (os.path.join(root, "fgnn-artifacts_amd"), mode, argv)
+''' % (os.path.join(root, "fgnn-artifacts_amd"), rc)
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(tmp_path))
     assert p.returncode == 0 and "accepted" in p.stdout, p.stdout[-1500:] + p.stderr[-3000:]
 

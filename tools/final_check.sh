@@ -7,7 +7,7 @@ python -m pytest tests -q -m gpu -x > $O/gpu_tests.log 2>&1; rc=$?; echo "pytest
 [ $rc -ne 0 ] && { grep -n "Error\|assert\|error" $O/gpu_tests.log | head -20; exit $rc; }
 python __graft_entry__.py smoke 2>&1 | tail -2
 for i in 1 2; do
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_s20_$i.json 2> $O/bench_s20_$i.err || echo "bench failed"
+python3 bench.py --gpus 1 --full --steps 20 --warmup 5 > $O/bench_s20_$i.json 2> $O/bench_s20_$i.err || echo "bench failed"
 python3 -c "
 import json
 d=json.loads(open('$O/bench_s20_$i.json').read().strip().splitlines()[-1])

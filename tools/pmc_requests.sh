@@ -9,7 +9,7 @@ wls=${@:-papers100M twitter uk-2006-05}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$tag; mkdir -p $O
 for wl in $wls; do
-  timeout -k 10 500 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace --output-format csv -d $O/${wl}_req -- python3 bench.py --workload $wl --steps 20 --warmup 3 --windows 1 --no-overlap --no-cpu-baseline --timed-only > $O/${wl}_req.log 2>&1 || { tail -5 $O/${wl}_req.log; exit 1; }
+  timeout -k 10 500 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace --output-format csv -d $O/${wl}_req -- python3 bench.py --full --workload $wl --steps 20 --warmup 3 --windows 1 --no-overlap --no-cpu-baseline --timed-only > $O/${wl}_req.log 2>&1 || { tail -5 $O/${wl}_req.log; exit 1; }
   echo "$wl done"
 done
 python3 tools/pmc_requests_summary.py $O $wls > $O/pmc_requests.json 2> $O/pmc_requests.err; tail -3 $O/pmc_requests.err

@@ -12,7 +12,7 @@ from collections import defaultdict
 O = sys.argv[1]
 GATHER = ("gather_rows16_kernel", "gather_rows_elem_kernel")
 out = {"command": "rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --kernel-trace --output-format csv -- python3 bench.py "
-                  "--workload <w> --steps 20 --warmup 3 --windows 1 --no-overlap --no-cpu-baseline --timed-only",
+                  "--full --workload <w> --steps 20 --warmup 3 --windows 1 --no-overlap --no-cpu-baseline --timed-only",
        "unit": "fabric requests (L2 -> memory side) per batch; sampler side = every kernel of a batch but the feature gather",
        "workloads": {}}
 for wl in sys.argv[2:]:
