@@ -247,6 +247,135 @@ class WeightedSAGEConv(nn.Module):
         return z / th.where(z_norm == 0, th.ones_like(z_norm), z_norm)
 
 
+def _fused_layers_apply(block, h):
+    """the rule FusedSAGEConv.forward uses: the HIP path for fp32 CUDA features and int32 COO indices with the library
+    present, the op-by-op arithmetic otherwise"""
+    return (_fused_aggregate is not None and h.is_cuda and h.dtype == th.float32
+            and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32)
+
+
+class _FusedGraphConvFn(th.autograd.Function):
+    """GraphConv(norm='both') as ONE autograd node: both degree vectors from one pass over the edges
+    (fgnn_block_degrees), D_out^-1/2 and D_in^-1/2 inside the aggregation (fgnn_block_aggregate_scaled: the source
+    factor folded into the edge weight, the destination factor applied at the flush), then one GEMM with bias.  No
+    scaled copy of h -- num_src x D, the largest tensor of the step -- is written, kept alive for the backward pass or
+    read back by it; the input gradient is the same launch with the indices, degree vectors and modes swapped.  Same
+    arithmetic as GraphConv (fp32; the order of the float additions differs: rtol 1e-4)."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, block, num_dst):
+        from fgnn_hip.nn import aggregate_scaled_into, block_degrees
+        h = h.contiguous()
+        src_deg, dst_deg = block_degrees(block.row, block.col, h.shape[0], num_dst)
+        agg = th.zeros((num_dst, h.shape[1]), dtype=h.dtype, device=h.device)
+        aggregate_scaled_into(agg, h, block.row, block.col, None, src_deg, 1, dst_deg, 1)
+        ctx.save_for_backward(agg, weight, block.row, block.col, src_deg, dst_deg)
+        ctx.num_src = h.shape[0]
+        return th.addmm(bias, agg, weight.t())
+
+    @staticmethod
+    def backward(ctx, gout):
+        from fgnn_hip.nn import aggregate_scaled_into
+        agg, weight, row, col, src_deg, dst_deg = ctx.saved_tensors
+        gout = gout.contiguous()
+        gw = _weight_grad(gout, agg) if ctx.needs_input_grad[1] else None
+        gb = gout.sum(0) if ctx.needs_input_grad[2] else None
+        gh = None
+        if ctx.needs_input_grad[0]:
+            gagg = gout.mm(weight)
+            gh = th.zeros((ctx.num_src, agg.shape[1]), dtype=gagg.dtype, device=gagg.device)
+            aggregate_scaled_into(gh, gagg, col, row, None, dst_deg, 1, src_deg, 1)
+        return gh, gw, gb, None, None
+
+
+class FusedGraphConv(nn.Module):
+    """GraphConv with the whole layer as one autograd node (_FusedGraphConvFn); the same parameters under the same
+    names (fc.weight, fc.bias), so state dicts load both ways.  Falls back to GraphConv's op-by-op arithmetic off the
+    GPU / without the HIP library / for other dtypes.  activate=False returns the pre-activation (the caller fuses the
+    ReLU with its dropout)."""
+
+    def __init__(self, in_feats, out_feats, activation=None):
+        super().__init__()
+        self.fc = TallLinear(in_feats, out_feats, bias=True)
+        self.activation = activation
+
+    def forward(self, block, h, activate=True):
+        if _fused_layers_apply(block, h):
+            out = _FusedGraphConvFn.apply(h, self.fc.weight, self.fc.bias, block, block.number_of_dst_nodes())
+        else:
+            row = block.row.long()
+            out_deg = th.zeros(h.shape[0], dtype=h.dtype, device=h.device).index_add_(
+                0, row, th.ones_like(row, dtype=h.dtype)).clamp(min=1)
+            h = h * out_deg.pow(-0.5).unsqueeze(1)
+            agg = _sum_to_dst(block, h) * _in_degree(block, h.dtype).clamp(min=1).pow(-0.5).unsqueeze(1)
+            out = self.fc(agg)
+        return self.activation(out) if self.activation and activate else out
+
+
+class _WeightedMeanCatFn(th.autograd.Function):
+    """z = [sum_e w_e q_u / max(sum_e w_e, 1) | h_dst]: PinSAGE's weighted neighbour mean written straight into the left
+    column block of the concatenation (weight sums by fgnn_block_degrees, the division inside
+    fgnn_block_aggregate_scaled), the destinations' own rows copied into the right block.  Backward: the left block of
+    the upstream gradient is read in place through its row stride.  The edge weights are visit counts: no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, h, block, w, num_dst):
+        from fgnn_hip.nn import aggregate_scaled_into, block_degrees
+        hidden, din = q.shape[1], h.shape[1]
+        _, ws = block_degrees(block.row, block.col, q.shape[0], num_dst, edge_weight=w, want_src=False)
+        z = th.empty((num_dst, hidden + din), dtype=q.dtype, device=q.device)
+        z[:, :hidden] = 0
+        aggregate_scaled_into(z[:, :hidden], q if q.stride(1) == 1 else q.contiguous(), block.row, block.col, w,
+                              dst_deg=ws, dst_mode=2)
+        z[:, hidden:] = h[:num_dst]
+        ctx.save_for_backward(block.row, block.col, w, ws)
+        ctx.shape = (q.shape[0], h.shape[0], hidden, din)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        from fgnn_hip.nn import aggregate_scaled_into
+        row, col, w, ws = ctx.saved_tensors
+        nq, nh, hidden, din = ctx.shape
+        if gz.stride(1) != 1 or gz.stride(0) < gz.shape[1]:
+            gz = gz.contiguous()
+        gq = gh = None
+        if ctx.needs_input_grad[0]:
+            gq = th.zeros((nq, hidden), dtype=gz.dtype, device=gz.device)
+            aggregate_scaled_into(gq, gz[:, :hidden], col, row, w, src_deg=ws, src_mode=2)
+        if ctx.needs_input_grad[1]:
+            gh = th.zeros((nh, din), dtype=gz.dtype, device=gz.device)
+            gh[:gz.shape[0]] = gz[:, hidden:]
+        return gq, gh, None, None, None
+
+
+class FusedWeightedSAGEConv(nn.Module):
+    """WeightedSAGEConv on the fused kernels: the weighted mean lands in its half of the concatenation in one launch
+    (_WeightedMeanCatFn), ReLU + row normalisation are one launch each way (fgnn_relu_l2norm); the GEMMs and the two
+    dropouts stay torch ops.  Same parameters under the same names (Q.*, W.*); falls back to WeightedSAGEConv's
+    arithmetic off the GPU / without the HIP library / for other dtypes."""
+
+    def __init__(self, in_feats, hidden, out_feats, dropout):
+        super().__init__()
+        self.Q = TallLinear(in_feats, hidden)
+        self.W = TallLinear(in_feats + hidden, out_feats)
+        self.dropout = nn.Dropout(dropout)
+
+    def forward(self, block, h):
+        num_dst = block.number_of_dst_nodes()
+        w = block.edata["weights"].to(h.dtype)
+        q = F.relu(self.Q(self.dropout(h)))
+        if _fused_layers_apply(block, h):
+            from fgnn_hip.nn import relu_l2norm
+            z = _WeightedMeanCatFn.apply(q, h, block, w.contiguous(), num_dst)
+            return relu_l2norm(self.W(self.dropout(z)))
+        n = _sum_to_dst(block, q, w)
+        ws = _in_degree(block, h.dtype, w).clamp(min=1).unsqueeze(1)
+        z = F.relu(self.W(self.dropout(th.cat([n / ws, h[:num_dst]], 1))))
+        z_norm = z.norm(2, 1, keepdim=True)
+        return z / th.where(z_norm == 0, th.ones_like(z_norm), z_norm)
+
+
 class SAGE(nn.Module):
     def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True):
         super().__init__()
@@ -274,15 +403,34 @@ class SAGE(nn.Module):
 
 
 class GCN(nn.Module):
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout):
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True):
         super().__init__()
         dims = [in_feats] + [n_hidden] * (n_layers - 1) + [n_classes]
-        self.layers = nn.ModuleList(GraphConv(dims[i], dims[i + 1], F.relu if i < n_layers - 1 else None)
+        # fused=False: the op-by-op layer (a dozen torch ops around one aggregation launch)
+        conv = FusedGraphConv if fused else GraphConv
+        self.fused = fused
+        self.layers = nn.ModuleList(conv(dims[i], dims[i + 1], F.relu if i < n_layers - 1 else None)
                                     for i in range(n_layers))
         self.dropout = nn.Dropout(dropout)
+        # as SAGE: set by a training loop that uses fgnn_hip.nn.Adam; the fused model then runs an inner layer's ReLU and
+        # the next layer's dropout as ONE launch (fgnn_relu_dropout) with a mask keyed by the device-side step count
+        self.dropout_step = None
+        self.dropout_seed = 0x5A4D47
 
     def forward(self, blocks, x):
         h = x
+        if self.fused and self.dropout_step is not None:
+            from fgnn_hip.nn import relu_dropout
+            for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+                if i == len(self.layers) - 1:
+                    h = layer(block, h)
+                    break
+                h = layer(block, h, activate=False)
+                if h.is_cuda and h.dtype == th.float32 and h.numel() % 4 == 0:
+                    h = relu_dropout(h, self.dropout.p, self.training, self.dropout_seed, self.dropout_step, i)
+                else:
+                    h = self.dropout(F.relu(h))
+            return h
         for i, (layer, block) in enumerate(zip(self.layers, blocks)):
             if i != 0:
                 h = self.dropout(h)
@@ -291,10 +439,11 @@ class GCN(nn.Module):
 
 
 class PinSAGE(nn.Module):
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout):
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True):
         super().__init__()
         dims = [in_feats] + [n_hidden] * (n_layers - 1) + [n_classes]
-        self.layers = nn.ModuleList(WeightedSAGEConv(dims[i], n_hidden, dims[i + 1], dropout) for i in range(n_layers))
+        conv = FusedWeightedSAGEConv if fused else WeightedSAGEConv
+        self.layers = nn.ModuleList(conv(dims[i], n_hidden, dims[i + 1], dropout) for i in range(n_layers))
 
     def forward(self, blocks, x):
         h = x

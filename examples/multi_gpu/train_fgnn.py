@@ -43,7 +43,7 @@ def build_parser():
     ap.add_argument("--report-acc", type=int, default=0,
                     help="trainer 0: validation accuracy every N of its steps and test accuracy at the end (the "
                          "reference's --report-acc, multi_gpu/train_graphsage.py:65,214-220,344-347,395-397); 0: off")
-    ap.add_argument("--op-by-op", action="store_true", help="graphsage: the op-by-op layers instead of the fused ones")
+    ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
     ap.add_argument("--sample-type", default=None)
     ap.add_argument("--fanout", nargs="+", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=8000)
@@ -145,7 +145,7 @@ def run_train(worker_id, rc):
     sam.wait_for_sampler_ready(barrier)
     sam.train_init(worker_id, ctx)
     num_layer = rc["num_layer"]
-    kw = dict(fused=False) if rc["op_by_op"] and rc["model"] == "graphsage" else {}
+    kw = dict(fused=False) if rc["op_by_op"] else {}
     model = MODELS[rc["model"]](sam.feat_dim(), rc["num_hidden"], sam.num_class(), num_layer, rc["dropout"], **kw).to(dev)
     accuracy = None
     if rc["report_acc"] and worker_id == 0 and rc["model"] != "pinsage":
@@ -255,7 +255,7 @@ def main():
         # (one CPU thread here: an OpenMP pool created by the parent would not survive the fork)
         torch.set_num_threads(1)
         torch.manual_seed(0)
-        kw = dict(fused=False) if rc["op_by_op"] and rc["model"] == "graphsage" else {}
+        kw = dict(fused=False) if rc["op_by_op"] else {}
         rc["global_cpu_model"] = MODELS[rc["model"]](sam.feat_dim(), rc["num_hidden"], sam.num_class(), rc["num_layer"],
                                                      rc["dropout"], **kw)
         rc["global_cpu_model"].share_memory()

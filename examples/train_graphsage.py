@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "examples"))
 import samgraph.torch as sam  # noqa: E402
 
 
-from models import MODELS, SAGE  # noqa: E402  (examples/models.py: torch-op layers on the engine's COO blocks)
+from models import MODELS  # noqa: E402  (examples/models.py: torch-op layers on the engine's COO blocks)
 
 
 def main():
@@ -61,7 +61,7 @@ def main():
     ap.add_argument("--report-acc", type=int, default=0,
                     help="validation accuracy every N steps and test accuracy at the end (the reference's --report-acc, "
                          "multi_gpu/train_graphsage.py:65,344-347,395-397); 0: off")
-    ap.add_argument("--op-by-op", action="store_true", help="the op-by-op SAGE layers instead of the fused ones")
+    ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
     ap.add_argument("--cache-policy", default="pre_sample",
                     help="a key of sam.cache_policies: pre_sample, presample_static, degree, ..., or dynamic_cache "
                          "(arch4 only: the cache is the previous batch's feature tensor; khop0 / khop1 / weighted_khop, "
@@ -104,11 +104,8 @@ def main():
         sam.start()
     dev = th.device(trainer_ctx)
     num_layer = args.num_layer if args.model == "pinsage" else len(args.fanout)
-    if args.model == "graphsage":
-        model = SAGE(sam.feat_dim(), args.num_hidden, sam.num_class(), num_layer, args.dropout,
-                     fused=not args.op_by_op).to(dev)
-    else:
-        model = MODELS[args.model](sam.feat_dim(), args.num_hidden, sam.num_class(), num_layer, args.dropout).to(dev)
+    model = MODELS[args.model](sam.feat_dim(), args.num_hidden, sam.num_class(), num_layer, args.dropout,
+                               fused=not args.op_by_op).to(dev)
     get_blocks = sam.get_dgl_blocks_with_weights if args.model == "pinsage" else sam.get_dgl_blocks
     accuracy = None
     if args.report_acc and args.model != "pinsage":

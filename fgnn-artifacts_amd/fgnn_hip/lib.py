@@ -46,6 +46,7 @@ EXPORTS = [
     "fgnn_cache_table_replace", "fgnn_get_miss_cache_index", "fgnn_gather_rows", "fgnn_gather_rows_masked", "fgnn_gather_rows_shared", "fgnn_extract_fused", "fgnn_extract_fused_grid", "fgnn_extract_fused_link_grid", "fgnn_block_aggregate", "fgnn_block_aggregate_ex", "fgnn_batch_set_feat_row_mask",
     "fgnn_sage_finish_z", "fgnn_sage_grad_prep", "fgnn_relu_dropout", "fgnn_relu_dropout_backward",
     "fgnn_softmax_xent_scratch_bytes", "fgnn_softmax_xent", "fgnn_adam_step",
+    "fgnn_block_degrees", "fgnn_block_aggregate_scaled", "fgnn_relu_l2norm", "fgnn_relu_l2norm_backward",
 ]
 
 _lib = None

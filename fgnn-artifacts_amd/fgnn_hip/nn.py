@@ -132,6 +132,79 @@ def relu_dropout(x, p, training, seed=0x5A4D47, d_step=None, tag=0):
     return _ReluDropout.apply(x, float(p), int(seed), d_step, int(tag))
 
 
+# ---- fused GCN / PinSAGE layers (csrc/gnn_layers.hip) ----------------------------------------------------------------------
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def block_degrees(row, col, num_src, num_dst, edge_weight=None, want_src=True):
+    """(src_deg or None, dst_deg), fp32, one launch over the edges: src_deg[row[e]] += 1 (GraphConv's out-degrees) and
+    dst_deg[col[e]] += edge_weight[e] if edge_weight is given, else 1 (in-degrees / PinSAGE's weight sums)."""
+    assert row.dtype == torch.int32 and col.dtype == torch.int32
+    assert row.is_contiguous() and col.is_contiguous() and row.numel() == col.numel()
+    if edge_weight is not None:
+        assert edge_weight.dtype == torch.float32 and edge_weight.is_contiguous() and edge_weight.numel() == col.numel()
+    # both vectors out of one zeroed buffer: one fill
+    buf = torch.zeros((num_src if want_src else 0) + num_dst, dtype=torch.float32, device=col.device)
+    src_deg, dst_deg = (buf[:num_src], buf[num_src:]) if want_src else (None, buf)
+    _lib._check(_lib.load().fgnn_block_degrees(_ptr(row), _ptr(col), _ptr(edge_weight), C.c_size_t(col.numel()),
+                                               _ptr(src_deg), _ptr(dst_deg), _st(col)), "fgnn_block_degrees")
+    return src_deg, dst_deg
+
+
+def aggregate_scaled_into(out, h, src_idx, dst_idx, edge_weight=None, src_deg=None, src_mode=0, dst_deg=None, dst_mode=0):
+    """out[dst_idx[e]] += f_dst(dst_deg[dst_idx[e]]) * edge_weight[e] * f_src(src_deg[src_idx[e]]) * h[src_idx[e]] into a
+    caller-initialised fp32 tensor, no autograd (modes: 0 factor 1, 1 rsqrt(max(d, 1)), 2 1 / max(d, 1)).  `out` AND `h`
+    may be column blocks of wider row-major matrices (unit stride inside a row).  The backward pass of a layer is the
+    same call with the index tensors, the degree vectors and the modes swapped."""
+    assert h.dtype == torch.float32 and out.dtype == torch.float32
+    assert h.dim() == 2 and h.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
+    assert src_idx.dtype == torch.int32 and dst_idx.dtype == torch.int32
+    assert src_idx.is_contiguous() and dst_idx.is_contiguous() and src_idx.numel() == dst_idx.numel()
+    for t in (edge_weight, src_deg, dst_deg):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    _lib._check(_lib.load().fgnn_block_aggregate_scaled(
+        _ptr(src_idx), _ptr(dst_idx), _ptr(edge_weight), C.c_size_t(src_idx.numel()), _ptr(h), C.c_size_t(h.stride(0)),
+        C.c_size_t(h.shape[1]), _ptr(out), C.c_size_t(out.stride(0)), _ptr(src_deg), C.c_int(src_mode), _ptr(dst_deg),
+        C.c_int(dst_mode), _st(h)), "fgnn_block_aggregate_scaled")
+    return out
+
+
+class _ReluL2Norm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        rows, dim = x.shape
+        out = torch.empty((rows, dim), dtype=torch.float32, device=x.device)
+        inv = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _lib._check(_lib.load().fgnn_relu_l2norm(_ptr(x), C.c_size_t(x.stride(0)), _ptr(out), C.c_size_t(dim), _ptr(inv),
+                                                 C.c_size_t(rows), C.c_size_t(dim), _st(x)), "fgnn_relu_l2norm")
+        ctx.save_for_backward(out, inv)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        out, inv = ctx.saved_tensors
+        if gout.stride(1) != 1 or gout.stride(0) < gout.shape[1]:
+            gout = gout.contiguous()
+        rows, dim = out.shape
+        gx = torch.empty_like(out)
+        _lib._check(_lib.load().fgnn_relu_l2norm_backward(_ptr(out), C.c_size_t(dim), _ptr(inv), _ptr(gout),
+                                                          C.c_size_t(gout.stride(0)), _ptr(gx), C.c_size_t(dim),
+                                                          C.c_size_t(rows), C.c_size_t(dim), _st(out)),
+                    "fgnn_relu_l2norm_backward")
+        return gx
+
+
+def relu_l2norm(x):
+    """z = relu(x); z / where(||z|| == 0, 1, ||z||) row by row as one launch (and one in the backward pass); x fp32
+    [rows, dim] with unit stride inside a row."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    return _ReluL2Norm.apply(x)
+
+
 class _XentWs:
     """scratch of fgnn_softmax_xent per (device, n): arrival counter (zeroed once) + row losses"""
     cache = {}

@@ -330,6 +330,30 @@ int fgnn_block_aggregate_ex(const uint32_t *src_index, const uint32_t *dst_index
                             size_t num_edge, const float *h, size_t dim, float *out, size_t out_ld, float *in_degree,
                             void *stream);
 
+/* ---- fused GCN / PinSAGE layers (csrc/gnn_layers.hip; examples/models.py FusedGraphConv, FusedWeightedSAGEConv) -------
+ * fp32, no host synchronisation, no allocation; a zero size returns FGNN_OK without a launch, a null, zero-dim,
+ * short-leading-dimension or misaligned argument FGNN_EINVAL before any launch. */
+/* Both degree vectors of a block in one pass over the edges, into caller-zeroed arrays:
+ *   src_deg[src_index[e]] += 1                               (src_deg NULL: not wanted; always an edge count)
+ *   dst_deg[dst_index[e]] += edge_weight ? edge_weight[e] : 1
+ * One atomic per (wave, run of equal destinations); any order of dst_index gives the same sums. */
+int fgnn_block_degrees(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight, size_t num_edge,
+                       float *src_deg, float *dst_deg, void *stream);
+/* out[dst_index[e], :] += f_dst(dst_deg[dst_index[e]]) * edge_weight[e] * f_src(src_deg[src_index[e]]) * h[src_index[e], :]
+ * with f by mode: 0 -> 1, 1 -> rsqrt(max(d, 1)), 2 -> 1 / max(d, 1) (a degree vector may be NULL for mode 0).  h and out
+ * may be column blocks of wider row-major matrices (h_ld, out_ld >= dim elements); out is initialised by the caller.
+ * The backward pass is the same call with the index arrays, the degree vectors and the modes swapped. */
+int fgnn_block_aggregate_scaled(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
+                                size_t num_edge, const float *h, size_t h_ld, size_t dim, float *out, size_t out_ld,
+                                const float *src_deg, int src_mode, const float *dst_deg, int dst_mode, void *stream);
+/* out = relu(x) / ||relu(x)||_2 row by row (a row without a positive entry stays zero); inv_norm[rows] receives
+ * 1 / norm (1 for zero rows) for the backward pass.  out must not alias x. */
+int fgnn_relu_l2norm(const float *x, size_t x_ld, float *out, size_t out_ld, float *inv_norm, size_t rows, size_t dim,
+                     void *stream);
+/* gx = (gout - out <gout, out>) * inv_norm where out > 0, else 0 (zero-norm rows: 0, as torch defines it) */
+int fgnn_relu_l2norm_backward(const float *out, size_t out_ld, const float *inv_norm, const float *gout, size_t gout_ld,
+                              float *gx, size_t gx_ld, size_t rows, size_t dim, void *stream);
+
 /* ---- fused pieces of a GraphSAGE training step (consumer side, csrc/train_ops.hip) ----------------------------------
  * Elementwise work a training step otherwise does with two to four framework ops each; one launch apiece because the
  * step is replayed as a captured HIP graph, where every node costs the GPU 15-20 us whatever it does.  fp32, the same

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
-"""Where does a GraphSAGE training step (torch ops on the engine's COO blocks) spend GPU time?  Synthetic blocks of
-the papers100M-shaped batch size.  Profiling aid."""
+"""Where does a training step (the layers of examples/models.py on the engine's COO blocks) spend GPU time?
+Default (--model graphsage): synthetic blocks of the papers100M-shaped batch size.  --model gcn / pinsage: the blocks
+of one real batch of bench.py's twitter / uk-2006-05 workload (same graph, train set and sampler), the op-by-op and the
+fused model stepped in alternation in this process (--ab alternations of --ab-steps steps, medians and spread per
+model), then the per-kernel table of the --fused one.  Profiling aid."""
+import argparse
 import os
 import sys
 
@@ -11,7 +15,109 @@ from torch.profiler import ProfilerActivity, profile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
 sys.path.insert(0, os.path.join(ROOT, "fgnn-artifacts_amd"))
-from models import SAGE  # noqa: E402
+from models import MODELS, SAGE  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--model", default="graphsage", choices=["graphsage", "gcn", "pinsage"])
+ap.add_argument("--fused", type=int, default=None, choices=[0, 1],
+                help="the fused layers (1) or the op-by-op ones (0); default 1 (graphsage: SAGE_FUSED)")
+ap.add_argument("--ab", type=int, default=5, help="gcn / pinsage: alternations of the op-by-op and the fused model")
+ap.add_argument("--ab-steps", type=int, default=50)
+ap.add_argument("--workload", default=None, help="gcn / pinsage: bench.py workload the batch comes from")
+args = ap.parse_args()
+if args.fused is not None:
+    os.environ["SAGE_FUSED"] = str(args.fused)
+
+
+def real_batch_blocks(workload, dev):
+    """the COO blocks (outermost first), labels and feature width of ONE batch that bench.py's sampler draws for
+    `workload`: same generated graph, train set and sampler configuration (benchlib/single.py)"""
+    sys.path.insert(0, ROOT)
+    from benchlib.common import SAMPLE_TYPES, WORKLOADS, gen_graph_on_gpu, gen_prefix_on_gpu, gen_train_set, lib
+    w = WORKLOADS[workload]
+    indptr, indices, num_edge = gen_graph_on_gpu(w["num_node"], w["num_edge"], 42, dev)
+    prefix = gen_prefix_on_gpu(indptr, num_edge, 11, dev) if w["sample_type"] == "weighted_khop_prefix" else None
+    sampler = lib.Sampler(indptr, indices, w["fanout"], w["batch_size"], sample_type=SAMPLE_TYPES[w["sample_type"]],
+                          seed=0x5A4D47, prob_prefix=prefix, walk_len=w.get("walk_len", 3),
+                          num_walks=w.get("num_walks", 4), restart_prob=w.get("restart_prob", 0.5))
+    bt = sampler.new_batch()
+    seeds = gen_train_set(None, w, dev)[:w["batch_size"]]
+    sampler.sample(seeds, 0, bt)
+    bt.finish()
+    m = bt.wait()
+    blocks = []
+    for l in range(m.num_layers):
+        row, col, nsrc, ndst = bt.graph(l)
+        b = Block(row.clone(), col.clone(), nsrc, ndst)
+        data = bt.graph_data(l)
+        if data is not None:
+            b.edata["weights"] = data.clone()
+        blocks.append(b)
+    blocks.sort(key=lambda b: -b.nsrc)
+    assert all(a.ndst == b.nsrc for a, b in zip(blocks, blocks[1:])), [(b.nsrc, b.ndst) for b in blocks]
+    del sampler, bt, indptr, indices, prefix
+    torch.cuda.empty_cache()
+    return blocks, w
+
+
+def ab_main():
+    """--model gcn / pinsage: the op-by-op model (the baseline) against the fused one, trained as benchlib/pipeline.py
+    trains (fgnn_hip.nn.Adam, fgnn_softmax_xent, dropout_step set, dropout 0.5, hidden 256)"""
+    import statistics
+    from fgnn_hip.nn import Adam, softmax_xent
+    dev = "cuda:0"
+    torch.cuda.set_device(0)
+    workload = args.workload or {"gcn": "twitter", "pinsage": "uk-2006-05"}[args.model]
+    blocks, w = real_batch_blocks(workload, dev)
+    print("%s batch of %s: %s" % (args.model, workload, ", ".join(
+        "%d src -> %d dst, %d edges" % (b.nsrc, b.ndst, b.row.numel()) for b in blocks)))
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(blocks[0].nsrc, w["feat_dim"], device=dev, generator=g)
+    y = torch.randint(0, w["num_class"], (blocks[-1].ndst,), device=dev, generator=g)
+    steppers = {}
+    for fused in (0, 1):
+        torch.manual_seed(0)
+        model = MODELS[args.model](w["feat_dim"], 256, w["num_class"], len(blocks), 0.5, fused=bool(fused)).to(dev)
+        opt = Adam(model.parameters(), lr=0.003)
+        model.dropout_step = opt.step_count
+
+        def step(model=model, opt=opt):
+            out = model(blocks, x)
+            loss, grad = softmax_xent(out, y)
+            opt.zero_grad()
+            out.backward(grad)
+            opt.step()
+        steppers[fused] = step
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def run(step, n):
+        e0.record()
+        for _ in range(n):
+            step()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+    for fused in (0, 1):  # warm-up: lazy initialisation, GEMM selection (_weight_grad), allocator
+        run(steppers[fused], 10)
+    ms = {0: [], 1: []}
+    for _ in range(args.ab):
+        for fused in (0, 1):
+            ms[fused].append(run(steppers[fused], args.ab_steps))
+    for fused in (0, 1):
+        v = ms[fused]
+        print("fused=%d: median %.3f ms per step, min %.3f, max %.3f, spread %.3f  (%s)"
+              % (fused, statistics.median(v), min(v), max(v), max(v) - min(v), " ".join("%.3f" % t for t in v)))
+    gain = statistics.median(ms[0]) - statistics.median(ms[1])
+    print("op-by-op median - fused median = %.3f ms; spread of the op-by-op runs %.3f ms: %s"
+          % (gain, max(ms[0]) - min(ms[0]), "ACCEPT" if gain > max(ms[0]) - min(ms[0]) else "REJECT"))
+    which = 1 if args.fused is None else args.fused
+    with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+        for _ in range(5):
+            steppers[which]()
+        torch.cuda.synchronize()
+    print("per-kernel times of 5 steps, fused=%d" % which)
+    print(prof.key_averages().table(sort_by="self_cuda_time_total", row_limit=int(os.environ.get('ROWS', '30')),
+                                    max_name_column_width=70))
 
 
 class Block:
@@ -22,6 +128,10 @@ class Block:
     def number_of_dst_nodes(self):
         return self.ndst
 
+
+if args.model != "graphsage":
+    ab_main()
+    sys.exit(0)
 
 dev = "cuda:0"
 g = torch.Generator(device=dev)
