@@ -229,8 +229,11 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(AdamTensors t, float lr, f
   // the step count lives on the device (a captured graph replays this launch): everyone reads the OLD value, the last
   // workgroup to leave advances it (stream order makes the new value visible to the next launch)
   const unsigned long long step = *d_step + 1ull;
-  const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);
-  const float step_size = lr / bc1, rsq_bc2 = 1.0f / sqrtf(bc2);
+  // the bias corrections in double, once per thread: in fp32, 1 - b2^step cancels for b2 near 1 and a small step (b2 =
+  // 0.999, step 2: half an ulp of powf's result is 1.5e-5 of the difference and 7e-6 of the update); torch computes them
+  // in double on the host (tests/test_train_kernel_references_gpu.py holds the update to a float64 reference)
+  const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
+  const float step_size = (float)((double)lr / bc1), rsq_bc2 = (float)(1.0 / sqrt(bc2));
   for (int k = 0; k < t.count; ++k) {
     float *p = t.p[k], *m = t.m[k], *v = t.v[k];
     const float *g = t.g[k];
@@ -352,7 +355,8 @@ extern "C" int fgnn_adam_step(float *const *params, const float *const *grads, f
   AdamTensors t;
   size_t most = 0;
   for (int k = 0; k < count; ++k) {
-    if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k]) return FGNN_EINVAL;
+    // (a tensor without elements may come with null pointers: torch hands them out for empty tensors)
+    if (numel[k] && (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k])) return FGNN_EINVAL;
     t.p[k] = params[k];
     t.g[k] = grads[k];
     t.m[k] = exp_avg[k];

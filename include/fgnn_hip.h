@@ -384,7 +384,8 @@ int fgnn_softmax_xent(const float *logits, size_t ld, const long long *labels, s
                       float *dlogits, size_t dl_ld, void *ws, size_t ws_bytes, void *stream);
 /* torch.optim.Adam's update (no amsgrad) for up to 8 tensors in one launch; h_* are HOST arrays of device pointers /
  * sizes.  d_step: device, two 64-bit words zeroed once by the caller -- [0] the number of steps taken (read, then
- * advanced by this launch), [1] scratch. */
+ * advanced by this launch), [1] scratch.  The bias corrections 1 - beta^step are computed in double (in fp32 they cancel
+ * for beta2 near 1 and small steps).  A tensor with h_numel[k] == 0 may have null pointers. */
 int fgnn_adam_step(float *const *h_params, const float *const *h_grads, float *const *h_exp_avg,
                    float *const *h_exp_avg_sq, const size_t *h_numel, int count, float lr, float beta1, float beta2,
                    float eps, float weight_decay, unsigned long long *d_step, void *stream);
