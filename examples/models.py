@@ -82,10 +82,16 @@ class TallLinear(nn.Linear):
         return super().forward(x)
 
 
+def _fused_layers_apply(block, h):
+    """the one rule for every layer here: the HIP path for fp32 CUDA features and int32 COO indices with the library
+    present, the op-by-op arithmetic otherwise"""
+    return (_fused_aggregate is not None and h.is_cuda and h.dtype == th.float32
+            and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32)
+
+
 def _sum_to_dst(block, h, weight=None):
     num_dst = block.number_of_dst_nodes()
-    if (_fused_aggregate is not None and h.is_cuda and h.dtype == th.float32 and getattr(block.row, "dtype", None) == th.int32
-            and block.col.dtype == th.int32):
+    if _fused_layers_apply(block, h):
         return _fused_aggregate(h, block.row, block.col, num_dst, weight)
     row, col = block.row.long(), block.col.long()
     msg = h[row] if weight is None else h[row] * weight.unsqueeze(1)
@@ -201,8 +207,7 @@ class FusedSAGEConv(nn.Module):
 
     def forward(self, block, h):
         num_dst = block.number_of_dst_nodes()
-        if (_fused_aggregate is not None and h.is_cuda and h.dtype == th.float32
-                and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32):
+        if _fused_layers_apply(block, h):
             return _FusedSageFn.apply(h, self.weight, self.bias, block, num_dst)
         agg = _sum_to_dst(block, h) / _in_degree(block, h.dtype).clamp(min=1).unsqueeze(1)
         return th.cat([h[:num_dst], agg], 1).mm(self.weight.t()) + self.bias
@@ -217,14 +222,19 @@ class GraphConv(nn.Module):
         self.fc = TallLinear(in_feats, out_feats, bias=True)
         self.activation = activation
 
-    def forward(self, block, h):
+    def conv(self, block, h):
+        """the layer before its activation"""
         row = block.row.long()
         out_deg = th.zeros(h.shape[0], dtype=h.dtype, device=h.device).index_add_(
             0, row, th.ones_like(row, dtype=h.dtype)).clamp(min=1)
         h = h * out_deg.pow(-0.5).unsqueeze(1)
         agg = _sum_to_dst(block, h) * _in_degree(block, h.dtype).clamp(min=1).pow(-0.5).unsqueeze(1)
-        out = self.fc(agg)
-        return self.activation(out) if self.activation else out
+        return self.fc(agg)
+
+    def forward(self, block, h, activate=True):
+        """activate=False returns the pre-activation (the caller fuses the ReLU with its dropout)"""
+        out = self.conv(block, h)
+        return self.activation(out) if self.activation and activate else out
 
 
 class WeightedSAGEConv(nn.Module):
@@ -245,13 +255,6 @@ class WeightedSAGEConv(nn.Module):
         z = F.relu(self.W(self.dropout(th.cat([n / ws, h[:num_dst]], 1))))
         z_norm = z.norm(2, 1, keepdim=True)
         return z / th.where(z_norm == 0, th.ones_like(z_norm), z_norm)
-
-
-def _fused_layers_apply(block, h):
-    """the rule FusedSAGEConv.forward uses: the HIP path for fp32 CUDA features and int32 COO indices with the library
-    present, the op-by-op arithmetic otherwise"""
-    return (_fused_aggregate is not None and h.is_cuda and h.dtype == th.float32
-            and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32)
 
 
 class _FusedGraphConvFn(th.autograd.Function):
@@ -288,28 +291,15 @@ class _FusedGraphConvFn(th.autograd.Function):
         return gh, gw, gb, None, None
 
 
-class FusedGraphConv(nn.Module):
+class FusedGraphConv(GraphConv):
     """GraphConv with the whole layer as one autograd node (_FusedGraphConvFn); the same parameters under the same
-    names (fc.weight, fc.bias), so state dicts load both ways.  Falls back to GraphConv's op-by-op arithmetic off the
-    GPU / without the HIP library / for other dtypes.  activate=False returns the pre-activation (the caller fuses the
-    ReLU with its dropout)."""
+    names (fc.weight, fc.bias), so state dicts load both ways.  Off the GPU / without the HIP library / for other dtypes
+    it IS GraphConv."""
 
-    def __init__(self, in_feats, out_feats, activation=None):
-        super().__init__()
-        self.fc = TallLinear(in_feats, out_feats, bias=True)
-        self.activation = activation
-
-    def forward(self, block, h, activate=True):
+    def conv(self, block, h):
         if _fused_layers_apply(block, h):
-            out = _FusedGraphConvFn.apply(h, self.fc.weight, self.fc.bias, block, block.number_of_dst_nodes())
-        else:
-            row = block.row.long()
-            out_deg = th.zeros(h.shape[0], dtype=h.dtype, device=h.device).index_add_(
-                0, row, th.ones_like(row, dtype=h.dtype)).clamp(min=1)
-            h = h * out_deg.pow(-0.5).unsqueeze(1)
-            agg = _sum_to_dst(block, h) * _in_degree(block, h.dtype).clamp(min=1).pow(-0.5).unsqueeze(1)
-            out = self.fc(agg)
-        return self.activation(out) if self.activation and activate else out
+            return _FusedGraphConvFn.apply(h, self.fc.weight, self.fc.bias, block, block.number_of_dst_nodes())
+        return super().conv(block, h)
 
 
 class _WeightedMeanCatFn(th.autograd.Function):
@@ -349,31 +339,20 @@ class _WeightedMeanCatFn(th.autograd.Function):
         return gq, gh, None, None, None
 
 
-class FusedWeightedSAGEConv(nn.Module):
+class FusedWeightedSAGEConv(WeightedSAGEConv):
     """WeightedSAGEConv on the fused kernels: the weighted mean lands in its half of the concatenation in one launch
     (_WeightedMeanCatFn), ReLU + row normalisation are one launch each way (fgnn_relu_l2norm); the GEMMs and the two
-    dropouts stay torch ops.  Same parameters under the same names (Q.*, W.*); falls back to WeightedSAGEConv's
-    arithmetic off the GPU / without the HIP library / for other dtypes."""
-
-    def __init__(self, in_feats, hidden, out_feats, dropout):
-        super().__init__()
-        self.Q = TallLinear(in_feats, hidden)
-        self.W = TallLinear(in_feats + hidden, out_feats)
-        self.dropout = nn.Dropout(dropout)
+    dropouts stay torch ops.  Same parameters under the same names (Q.*, W.*); off the GPU / without the HIP library /
+    for other dtypes it IS WeightedSAGEConv."""
 
     def forward(self, block, h):
-        num_dst = block.number_of_dst_nodes()
+        if not _fused_layers_apply(block, h):
+            return super().forward(block, h)
+        from fgnn_hip.nn import relu_l2norm
         w = block.edata["weights"].to(h.dtype)
         q = F.relu(self.Q(self.dropout(h)))
-        if _fused_layers_apply(block, h):
-            from fgnn_hip.nn import relu_l2norm
-            z = _WeightedMeanCatFn.apply(q, h, block, w.contiguous(), num_dst)
-            return relu_l2norm(self.W(self.dropout(z)))
-        n = _sum_to_dst(block, q, w)
-        ws = _in_degree(block, h.dtype, w).clamp(min=1).unsqueeze(1)
-        z = F.relu(self.W(self.dropout(th.cat([n / ws, h[:num_dst]], 1))))
-        z_norm = z.norm(2, 1, keepdim=True)
-        return z / th.where(z_norm == 0, th.ones_like(z_norm), z_norm)
+        z = _WeightedMeanCatFn.apply(q, h, block, w.contiguous(), block.number_of_dst_nodes())
+        return relu_l2norm(self.W(self.dropout(z)))
 
 
 class SAGE(nn.Module):

@@ -8,23 +8,26 @@
 // and col swapped is the backward pass (grad_h[row[e]] += w[e] * grad_out[col[e]]).  Sums in fp32; the order of the
 // additions is not fixed; against a float64 reference every output stays within (k + 8) 2^-23 of the sum of its terms'
 // magnitudes, k = the destination's edge count (tests/test_train_kernel_references_gpu.py; observed: 0.15 of that).
+// ONE kernel template serves the three entry points.  fgnn_block_aggregate / fgnn_block_aggregate_ex: the plain sum,
+// with the destinations' in-degrees counted on the way if asked for.  fgnn_block_aggregate_scaled (SCALED
+// instantiations; the fused GCN and PinSAGE layers): the layers' degree scalings ride along -- the per-source factor is
+// folded into the broadcast edge weight, the per-destination factor multiplies every flushed partial sum.  Both are
+// linear, so no scaled copy of h (num_src x D, the largest tensor of a step) is ever written, and the backward pass is
+// the same launch with indices, degree vectors and modes swapped.
 #include "fgnn_device.h"
 
 namespace fgnn {
 namespace {
 
-constexpr int kEdgesPerWave = 32;
-
 // Lane l owns dims l, l + 64, ... (P of them per pass over the edges): every load and every float atomic of a wave
 // instruction covers 64 consecutive floats.  All lanes run the edge loop (the shuffles need them), memory operations
-// are masked by `l + 64 p < dim`.
-template <int P>
-__global__ __launch_bounds__(kBlock) void block_aggregate_kernel(const uint32_t *__restrict__ src_idx,
-                                                                 const uint32_t *__restrict__ dst_idx,
-                                                                 const float *__restrict__ w,
-                                                                 const float *__restrict__ h, float *out,
-                                                                 size_t num_edge, uint32_t dim, uint32_t out_ld,
-                                                                 float *deg) {
+// are masked by `l + 64 p < dim`.  SCALED: lane i's weight is multiplied by its source's degree factor and the
+// destination factor of its segment travels beside it; the other instantiations carry neither.
+template <int P, bool SCALED>
+__global__ __launch_bounds__(kBlock) void block_aggregate_kernel(
+    const uint32_t *__restrict__ src_idx, const uint32_t *__restrict__ dst_idx, const float *__restrict__ w,
+    const float *__restrict__ h, float *out, size_t num_edge, uint32_t dim, uint32_t h_ld, uint32_t out_ld, float *deg,
+    const float *__restrict__ src_deg, int src_mode, const float *__restrict__ dst_deg, int dst_mode) {
   const size_t wave = (size_t)blockIdx.x * kWavesPerBlock + wave_id();
   const size_t e0 = wave * kEdgesPerWave;
   if (e0 >= num_edge) return;  // wave-uniform
@@ -35,10 +38,15 @@ __global__ __launch_bounds__(kBlock) void block_aggregate_kernel(const uint32_t 
   // issuing a dependent (index -> row) load chain per edge
   uint32_t my_src = 0, my_dst = 0;
   float my_w = 1.0f;
+  [[maybe_unused]] float my_fd = 1.0f;
   if (lane < cnt) {
     my_src = src_idx[e0 + lane];
     my_dst = dst_idx[e0 + lane];
     if (w) my_w = w[e0 + lane];
+    if constexpr (SCALED) {
+      if (src_mode) my_w *= degree_factor(src_deg[my_src], src_mode);
+      if (dst_mode) my_fd = degree_factor(dst_deg[my_dst], dst_mode);
+    }
   }
   // in-degrees on the way (deg != null): the first lane of every run of equal destinations adds the run's length --
   // one float atomic per (wave, destination) instead of an index_add_ pass of its own over the edges
@@ -46,11 +54,7 @@ __global__ __launch_bounds__(kBlock) void block_aggregate_kernel(const uint32_t 
     const uint32_t prev = __shfl_up(my_dst, 1, kWave);
     const bool head = lane < cnt && (lane == 0 || prev != my_dst);
     const unsigned long long heads = __ballot(head);
-    if (head) {
-      const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1)) << (lane + 1);
-      const uint32_t next = later ? (uint32_t)__builtin_ctzll(later) : cnt;
-      unsafeAtomicAdd(&deg[my_dst], (float)(next - lane));
-    }
+    if (head) unsafeAtomicAdd(&deg[my_dst], (float)run_length_at_head(heads, lane, cnt));
   }
   for (uint32_t dbase = 0; dbase < dim; dbase += kWave * P) {  // one trip for dim <= 64 P
     bool act[P];
@@ -61,18 +65,27 @@ __global__ __launch_bounds__(kBlock) void block_aggregate_kernel(const uint32_t 
       acc[q] = 0.0f;
     }
     uint32_t cur = __shfl(my_dst, 0, kWave);
+    [[maybe_unused]] float cur_fd = 1.0f;
+    if constexpr (SCALED) cur_fd = __shfl(my_fd, 0, kWave);
+    // what a flush adds for the partial sum a: the destination factor is applied here, once per segment
+    auto flushed = [&](float a) {
+      if constexpr (SCALED) return cur_fd * a;
+      else return a;
+    };
     constexpr uint32_t UN = 4;  // edges whose row loads are in flight together
     for (uint32_t i0 = 0; i0 < cnt; i0 += UN) {
       float v[UN][P];
       uint32_t c[UN];
       float we[UN];
+      [[maybe_unused]] float fd[UN];
 #pragma unroll
       for (uint32_t u = 0; u < UN; ++u) {
         const uint32_t i = i0 + u < cnt ? i0 + u : cnt - 1;  // clamp: the extra loads are discarded below
         const uint32_t sidx = __shfl(my_src, (int)i, kWave);
         c[u] = __shfl(my_dst, (int)i, kWave);
         we[u] = __shfl(my_w, (int)i, kWave);
-        const float *hp = h + (size_t)sidx * dim + dbase + lane;
+        if constexpr (SCALED) fd[u] = __shfl(my_fd, (int)i, kWave);
+        const float *hp = h + (size_t)sidx * h_ld + dbase + lane;
 #pragma unroll
         for (int q = 0; q < P; ++q) v[u][q] = act[q] ? hp[kWave * q] : 0.0f;
       }
@@ -83,10 +96,11 @@ __global__ __launch_bounds__(kBlock) void block_aggregate_kernel(const uint32_t 
           float *op = out + (size_t)cur * out_ld + dbase + lane;
 #pragma unroll
           for (int q = 0; q < P; ++q) {
-            if (act[q]) unsafeAtomicAdd(op + kWave * q, acc[q]);
+            if (act[q]) unsafeAtomicAdd(op + kWave * q, flushed(acc[q]));
             acc[q] = 0.0f;
           }
           cur = c[u];
+          if constexpr (SCALED) cur_fd = fd[u];
         }
 #pragma unroll
         for (int q = 0; q < P; ++q) acc[q] += we[u] * v[u][q];
@@ -95,8 +109,36 @@ __global__ __launch_bounds__(kBlock) void block_aggregate_kernel(const uint32_t 
     float *op = out + (size_t)cur * out_ld + dbase + lane;
 #pragma unroll
     for (int q = 0; q < P; ++q)
-      if (act[q]) unsafeAtomicAdd(op + kWave * q, acc[q]);
+      if (act[q]) unsafeAtomicAdd(op + kWave * q, flushed(acc[q]));
   }
+}
+
+// The one way to a launch: argument checks, grid, and the choice of instantiation (columns per lane by dim; SCALED by
+// entry point -- the scaled one keeps its instantiation for modes 0 / 0 too).
+int launch_block_aggregate(const char *what, bool scaled, const uint32_t *src_index, const uint32_t *dst_index,
+                           const float *edge_weight, size_t num_edge, const float *h, size_t h_ld, size_t dim, float *out,
+                           size_t out_ld, float *in_degree, const float *src_deg, int src_mode, const float *dst_deg,
+                           int dst_mode, void *stream) {
+  if (num_edge == 0) return FGNN_OK;
+  if (!src_index || !dst_index || !h || !out || dim == 0 || !fits_u32(dim) || h_ld < dim || !fits_u32(h_ld) ||
+      out_ld < dim || !fits_u32(out_ld))
+    return FGNN_EINVAL;
+  if (src_mode < 0 || src_mode > 2 || dst_mode < 0 || dst_mode > 2 || (src_mode && !src_deg) || (dst_mode && !dst_deg))
+    return FGNN_EINVAL;
+  if (!float_aligned(src_index) || !float_aligned(dst_index) || !float_aligned(edge_weight) || !float_aligned(h) ||
+      !float_aligned(out) || !float_aligned(in_degree) || !float_aligned(src_deg) || !float_aligned(dst_deg))
+    return FGNN_EINVAL;
+  const size_t waves = div_up(num_edge, (size_t)kEdgesPerWave);
+  const size_t blocks = div_up(waves, (size_t)kWavesPerBlock);
+  if (blocks > 0x7fffffffull) return FGNN_EINVAL;
+  using Kernel = decltype(&block_aggregate_kernel<1, false>);
+  static constexpr Kernel kernels[2][3] = {
+      {block_aggregate_kernel<1, false>, block_aggregate_kernel<2, false>, block_aggregate_kernel<4, false>},
+      {block_aggregate_kernel<1, true>, block_aggregate_kernel<2, true>, block_aggregate_kernel<4, true>}};
+  hipLaunchKernelGGL(kernels[scaled][dim <= 64 ? 0 : (dim <= 128 ? 1 : 2)], dim3(blocks), dim3(kBlock), 0,
+                     static_cast<hipStream_t>(stream), src_index, dst_index, edge_weight, h, out, num_edge, (uint32_t)dim,
+                     (uint32_t)h_ld, (uint32_t)out_ld, in_degree, src_deg, src_mode, dst_deg, dst_mode);
+  return launch_status(what);
 }
 
 }  // namespace
@@ -105,24 +147,20 @@ __global__ __launch_bounds__(kBlock) void block_aggregate_kernel(const uint32_t 
 extern "C" int fgnn_block_aggregate_ex(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
                                        size_t num_edge, const float *h, size_t dim, float *out, size_t out_ld,
                                        float *in_degree, void *stream) {
-  using namespace fgnn;
-  if (num_edge == 0) return FGNN_OK;
-  if (!src_index || !dst_index || !h || !out || dim == 0 || dim > 0xffffffffull || out_ld < dim || out_ld > 0xffffffffull)
-    return FGNN_EINVAL;
-  auto st = static_cast<hipStream_t>(stream);
-  const size_t waves = div_up(num_edge, (size_t)kEdgesPerWave);
-  const size_t blocks = div_up(waves, (size_t)kWavesPerBlock);
-#define FGNN_AGG(PP)                                                                                               \
-  hipLaunchKernelGGL((block_aggregate_kernel<PP>), dim3(blocks), dim3(kBlock), 0, st, src_index, dst_index,        \
-                     edge_weight, h, out, num_edge, (uint32_t)dim, (uint32_t)out_ld, in_degree)
-  if (dim <= 64) FGNN_AGG(1);
-  else if (dim <= 128) FGNN_AGG(2);
-  else FGNN_AGG(4);
-#undef FGNN_AGG
-  return launch_status(__func__);
+  return fgnn::launch_block_aggregate(__func__, false, src_index, dst_index, edge_weight, num_edge, h, dim, dim, out,
+                                      out_ld, in_degree, nullptr, 0, nullptr, 0, stream);
 }
 
 extern "C" int fgnn_block_aggregate(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
                                     size_t num_edge, const float *h, size_t dim, float *out, void *stream) {
-  return fgnn_block_aggregate_ex(src_index, dst_index, edge_weight, num_edge, h, dim, out, dim, nullptr, stream);
+  return fgnn::launch_block_aggregate(__func__, false, src_index, dst_index, edge_weight, num_edge, h, dim, dim, out, dim,
+                                      nullptr, nullptr, 0, nullptr, 0, stream);
+}
+
+extern "C" int fgnn_block_aggregate_scaled(const uint32_t *src_index, const uint32_t *dst_index,
+                                           const float *edge_weight, size_t num_edge, const float *h, size_t h_ld,
+                                           size_t dim, float *out, size_t out_ld, const float *src_deg, int src_mode,
+                                           const float *dst_deg, int dst_mode, void *stream) {
+  return fgnn::launch_block_aggregate(__func__, true, src_index, dst_index, edge_weight, num_edge, h, h_ld, dim, out,
+                                      out_ld, nullptr, src_deg, src_mode, dst_deg, dst_mode, stream);
 }

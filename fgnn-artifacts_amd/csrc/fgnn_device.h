@@ -289,6 +289,20 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
   return v;
 }
 
+// Runs of equal keys over a wave's first `cnt` lanes (one key per lane): `heads` = ballot of the lanes that start a run.
+// Returns the length of the run that starts at `lane`; meaningful on head lanes only.
+__device__ __forceinline__ uint32_t run_length_at_head(unsigned long long heads, uint32_t lane, uint32_t cnt) {
+  const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1)) << (lane + 1);
+  const uint32_t next = later ? (uint32_t)__builtin_ctzll(later) : cnt;
+  return next - lane;
+}
+
+// the GNN layers' degree scalings: 0 none, 1 d^-1/2, 2 1/d, both of max(d, 1) (nodes without an edge keep factor 1)
+__device__ __forceinline__ float degree_factor(float d, int mode) {
+  d = d < 1.0f ? 1.0f : d;
+  return mode == 1 ? rsqrtf(d) : (mode == 2 ? 1.0f / d : 1.0f);
+}
+
 // exclusive block scan of one value per thread (NW waves per block); *block_total gets the sum.
 // `sh` needs NW words.  Contains two barriers.
 template <int NW = kWavesPerBlock>
@@ -555,6 +569,11 @@ int launch_scan_block_sums(uint32_t *sums, size_t n, size_t *total64, uint32_t *
                            const size_t *d_items64 = nullptr);
 
 inline size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }
+// argument checks of the training-side entry points (block_aggregate.hip, gnn_layers.hip)
+inline bool float_aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+inline bool fits_u32(size_t v) { return v <= 0xffffffffull; }
+inline bool fits_rows(size_t v) { return v <= 0x7fffffffull; }  // row loops step a 32-bit counter by the grid's stride
+constexpr int kEdgesPerWave = 32;  // block_aggregate_kernel: edges a wave broadcasts from its lanes
 
 // Stable sort of n (key, value) uint32 pairs by key, ascending (defined in scan.hip): one launch up to 8 k pairs, five
 // up to 65 k, twelve beyond -- grids of independent workgroups.  keys_alt/vals_alt: n words each; ws:

@@ -3,26 +3,15 @@
 // example/samgraph/multi_gpu/train_gcn.py:24-47 / train_pinsage.py:24-75):
 //   fgnn_block_degrees          both degree vectors of a block (edge counts per source, edge counts or weight sums per
 //                               destination) in ONE pass over the edges -- two index_add_ passes op by op
-//   fgnn_block_aggregate_scaled block_aggregate_kernel (block_aggregate.hip) with the layers' degree scalings riding
-//                               along: the per-source factor is folded into the broadcast edge weight, the
-//                               per-destination factor multiplies every flushed partial sum.  Both are linear, so no
-//                               scaled copy of h (num_src x D, the largest tensor of a step) is ever written, and the
-//                               backward pass is the same launch with indices, degree vectors and modes swapped
 //   fgnn_relu_l2norm (+ _backward)   ReLU + row L2 normalisation, one wave per row, one launch each way -- relu, norm,
 //                               where and divide, each with a backward node of its own, op by op
+// The layers' aggregation with the degree scalings inside (fgnn_block_aggregate_scaled) is the SCALED instantiation of
+// the one aggregation kernel in block_aggregate.hip.
 // fp32 throughout; sums are not ordered (float atomics), results agree with the torch formulation to rounding.
 #include "fgnn_device.h"
 
 namespace fgnn {
 namespace {
-
-constexpr int kEdgesPerWave = 32;
-
-// the layers' degree scalings: 0 none, 1 d^-1/2, 2 1/d, both of max(d, 1) (nodes without an edge keep factor 1)
-__device__ __forceinline__ float degree_factor(float d, int mode) {
-  d = d < 1.0f ? 1.0f : d;
-  return mode == 1 ? rsqrtf(d) : (mode == 2 ? 1.0f / d : 1.0f);
-}
 
 // One lane per edge.  Sources are scattered: one float atomic per edge.  Destinations arrive seed-major, so a wave's 64
 // edges fall into a few runs of equal destination: one atomic per (wave, run) -- the run's length (ballot of the run
@@ -49,11 +38,7 @@ __global__ __launch_bounds__(kBlock) void block_degrees_kernel(const uint32_t *_
   const uint32_t cnt = (uint32_t)__popcll(__ballot(live));  // live lanes are the wave's first cnt
   if (heads == 0ull) return;                                // wave-uniform: no edge in this wave
   if (!WEIGHTED) {
-    if (head) {
-      const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1)) << (lane + 1);
-      const uint32_t next = later ? (uint32_t)__builtin_ctzll(later) : cnt;
-      unsafeAtomicAdd(&dst_deg[my_dst], (float)(next - lane));
-    }
+    if (head) unsafeAtomicAdd(&dst_deg[my_dst], (float)run_length_at_head(heads, lane, cnt));
   } else {
     // head of this lane's run = highest head bit at or below the lane (dead lanes: any value, they add nothing)
     const unsigned long long below = heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
@@ -66,79 +51,6 @@ __global__ __launch_bounds__(kBlock) void block_degrees_kernel(const uint32_t *_
     }
     const bool tail = live && (lane + 1 == cnt || ((heads >> (lane + 1)) & 1ull));
     if (tail) unsafeAtomicAdd(&dst_deg[my_dst], s);
-  }
-}
-
-// block_aggregate_kernel with a row stride for h and the two degree factors.  Lane l owns dims l, l + 64, ...; lane i
-// holds edge e0 + i, its weight already multiplied by the source factor and the destination factor of its segment
-// beside it; the edge loop broadcasts them with wave shuffles.
-template <int P>
-__global__ __launch_bounds__(kBlock) void block_aggregate_scaled_kernel(
-    const uint32_t *__restrict__ src_idx, const uint32_t *__restrict__ dst_idx, const float *__restrict__ w,
-    const float *__restrict__ h, float *out, size_t num_edge, uint32_t dim, uint32_t h_ld, uint32_t out_ld,
-    const float *__restrict__ src_deg, int src_mode, const float *__restrict__ dst_deg, int dst_mode) {
-  const size_t wave = (size_t)blockIdx.x * kWavesPerBlock + wave_id();
-  const size_t e0 = wave * kEdgesPerWave;
-  if (e0 >= num_edge) return;  // wave-uniform
-  const size_t e1 = e0 + kEdgesPerWave < num_edge ? e0 + kEdgesPerWave : num_edge;
-  const uint32_t lane = (uint32_t)lane_id();
-  const uint32_t cnt = (uint32_t)(e1 - e0);
-  uint32_t my_src = 0, my_dst = 0;
-  float my_w = 1.0f, my_fd = 1.0f;
-  if (lane < cnt) {
-    my_src = src_idx[e0 + lane];
-    my_dst = dst_idx[e0 + lane];
-    if (w) my_w = w[e0 + lane];
-    if (src_mode) my_w *= degree_factor(src_deg[my_src], src_mode);
-    if (dst_mode) my_fd = degree_factor(dst_deg[my_dst], dst_mode);
-  }
-  for (uint32_t dbase = 0; dbase < dim; dbase += kWave * P) {  // one trip for dim <= 64 P
-    bool act[P];
-    float acc[P];
-#pragma unroll
-    for (int q = 0; q < P; ++q) {
-      act[q] = dbase + lane + kWave * q < dim;
-      acc[q] = 0.0f;
-    }
-    uint32_t cur = __shfl(my_dst, 0, kWave);
-    float cur_fd = __shfl(my_fd, 0, kWave);
-    constexpr uint32_t UN = 4;  // edges whose row loads are in flight together
-    for (uint32_t i0 = 0; i0 < cnt; i0 += UN) {
-      float v[UN][P];
-      uint32_t c[UN];
-      float we[UN], fd[UN];
-#pragma unroll
-      for (uint32_t u = 0; u < UN; ++u) {
-        const uint32_t i = i0 + u < cnt ? i0 + u : cnt - 1;  // clamp: the extra loads are discarded below
-        const uint32_t sidx = __shfl(my_src, (int)i, kWave);
-        c[u] = __shfl(my_dst, (int)i, kWave);
-        we[u] = __shfl(my_w, (int)i, kWave);
-        fd[u] = __shfl(my_fd, (int)i, kWave);
-        const float *hp = h + (size_t)sidx * h_ld + dbase + lane;
-#pragma unroll
-        for (int q = 0; q < P; ++q) v[u][q] = act[q] ? hp[kWave * q] : 0.0f;
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < UN; ++u) {
-        if (i0 + u >= cnt) break;  // wave-uniform
-        if (c[u] != cur) {         // wave-uniform: segment boundary, flush the scaled partial sum
-          float *op = out + (size_t)cur * out_ld + dbase + lane;
-#pragma unroll
-          for (int q = 0; q < P; ++q) {
-            if (act[q]) unsafeAtomicAdd(op + kWave * q, cur_fd * acc[q]);
-            acc[q] = 0.0f;
-          }
-          cur = c[u];
-          cur_fd = fd[u];
-        }
-#pragma unroll
-        for (int q = 0; q < P; ++q) acc[q] += we[u] * v[u][q];
-      }
-    }
-    float *op = out + (size_t)cur * out_ld + dbase + lane;
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-      if (act[q]) unsafeAtomicAdd(op + kWave * q, cur_fd * acc[q]);
   }
 }
 
@@ -221,10 +133,6 @@ __global__ __launch_bounds__(kBlock) void relu_l2norm_bwd_kernel(const float *__
   }
 }
 
-inline bool float_aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-inline bool fits_u32(size_t v) { return v <= 0xffffffffull; }
-inline bool fits_rows(size_t v) { return v <= 0x7fffffffull; }  // the row loops step a 32-bit counter by the grid's stride
-
 // rows handled by a grid of waves with a stride: enough workgroups to fill the chip, no more
 inline size_t row_grid(size_t rows) {
   const size_t want = div_up(rows, (size_t)kWavesPerBlock), cap = (size_t)device_cu_count() * 8;
@@ -251,35 +159,6 @@ extern "C" int fgnn_block_degrees(const uint32_t *src_index, const uint32_t *dst
   else
     hipLaunchKernelGGL((block_degrees_kernel<false>), dim3(blocks), dim3(kBlock), 0, st, src_index, dst_index,
                        edge_weight, num_edge, src_deg, dst_deg);
-  return launch_status(__func__);
-}
-
-extern "C" int fgnn_block_aggregate_scaled(const uint32_t *src_index, const uint32_t *dst_index,
-                                           const float *edge_weight, size_t num_edge, const float *h, size_t h_ld,
-                                           size_t dim, float *out, size_t out_ld, const float *src_deg, int src_mode,
-                                           const float *dst_deg, int dst_mode, void *stream) {
-  using namespace fgnn;
-  if (num_edge == 0) return FGNN_OK;
-  if (!src_index || !dst_index || !h || !out || dim == 0 || !fits_u32(dim) || h_ld < dim || !fits_u32(h_ld) ||
-      out_ld < dim || !fits_u32(out_ld))
-    return FGNN_EINVAL;
-  if (src_mode < 0 || src_mode > 2 || dst_mode < 0 || dst_mode > 2 || (src_mode && !src_deg) || (dst_mode && !dst_deg))
-    return FGNN_EINVAL;
-  if (!float_aligned(src_index) || !float_aligned(dst_index) || !float_aligned(edge_weight) || !float_aligned(h) ||
-      !float_aligned(out) || !float_aligned(src_deg) || !float_aligned(dst_deg))
-    return FGNN_EINVAL;
-  const size_t waves = div_up(num_edge, (size_t)kEdgesPerWave);
-  const size_t blocks = div_up(waves, (size_t)kWavesPerBlock);
-  if (blocks > 0x7fffffffull) return FGNN_EINVAL;
-  auto st = static_cast<hipStream_t>(stream);
-#define FGNN_AGG(PP)                                                                                                 \
-  hipLaunchKernelGGL((block_aggregate_scaled_kernel<PP>), dim3(blocks), dim3(kBlock), 0, st, src_index, dst_index,    \
-                     edge_weight, h, out, num_edge, (uint32_t)dim, (uint32_t)h_ld, (uint32_t)out_ld, src_deg,         \
-                     src_mode, dst_deg, dst_mode)
-  if (dim <= 64) FGNN_AGG(1);
-  else if (dim <= 128) FGNN_AGG(2);
-  else FGNN_AGG(4);
-#undef FGNN_AGG
   return launch_status(__func__);
 }
 

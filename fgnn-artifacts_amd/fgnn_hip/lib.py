@@ -51,6 +51,26 @@ EXPORTS = [
 
 _lib = None
 
+# The training-side entry points (fgnn_hip/nn.py) as include/fgnn_hip.h declares them: return type, argument types.
+# Pointers travel as addresses (an int, a c_void_p or None), so the call sites pass data_ptr() values and plain numbers.
+_P, _Z, _I, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_float
+_PP, _PZ = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+_TRAIN_SIGNATURES = {
+    "fgnn_block_aggregate": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _P]),
+    "fgnn_block_aggregate_ex": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P]),
+    "fgnn_block_aggregate_scaled": (_I, [_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P]),
+    "fgnn_block_degrees": (_I, [_P, _P, _P, _Z, _P, _P, _P]),
+    "fgnn_relu_l2norm": (_I, [_P, _Z, _P, _Z, _P, _Z, _Z, _P]),
+    "fgnn_relu_l2norm_backward": (_I, [_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P]),
+    "fgnn_sage_finish_z": (_I, [_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P]),
+    "fgnn_sage_grad_prep": (_I, [_P, _Z, _P, _P, _P, _Z, _Z, _Z, _P]),
+    "fgnn_relu_dropout": (_I, [_P, _P, _Z, _F, C.c_uint64, _P, C.c_uint32, _P]),
+    "fgnn_relu_dropout_backward": (_I, [_P, _P, _P, _Z, _F, _P]),
+    "fgnn_softmax_xent_scratch_bytes": (_Z, [_Z]),
+    "fgnn_softmax_xent": (_I, [_P, _Z, _P, _Z, _Z, _P, _P, _Z, _P, _Z, _P]),
+    "fgnn_adam_step": (_I, [_PP, _PP, _PP, _PP, _PZ, _I, _F, _F, _F, _F, _F, _P, _P]),
+}
+
 
 class FgnnError(RuntimeError):
     pass
@@ -85,6 +105,9 @@ def load():
         L.fgnn_hashtable_d_num_items.argtypes = [C.c_void_p]
         L.fgnn_debug_set_scan_help_after.restype = None
         L.fgnn_debug_set_scan_help_after.argtypes = [C.c_int]
+        for name, (restype, argtypes) in _TRAIN_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         # (neither the library nor this binding reads a switch from the environment: tests that force the helping path of
         # the single-pass kernels call fgnn_debug_set_scan_help_after themselves, tests/conftest.py)
         _lib = L

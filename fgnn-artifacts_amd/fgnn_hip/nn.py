@@ -8,13 +8,34 @@ import torch
 from . import lib as _lib
 
 
-def _launch(src_idx, dst_idx, w, h, out):
+# Argument and return types of every entry point used here are declared once, in lib._TRAIN_SIGNATURES (applied by
+# lib.load()): the calls below pass addresses (lib._ptr: None = null) and plain numbers.
+_ptr = _lib._ptr
+
+
+def _st(t):
+    """the current stream of t's device"""
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _aggregate(out, h, src_idx, dst_idx, weight, in_degree=None, scaling=None):
+    """the one aggregation call: out[dst_idx[e]] += weight[e] * h[src_idx[e]] through fgnn_block_aggregate_ex (h
+    contiguous; in_degree optional), or, with scaling = (src_deg, src_mode, dst_deg, dst_mode), through
+    fgnn_block_aggregate_scaled (h with a row stride, degree factors inside)"""
     L = _lib.load()
-    st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-    _lib._check(L.fgnn_block_aggregate(C.c_void_p(src_idx.data_ptr()), C.c_void_p(dst_idx.data_ptr()),
-                                       C.c_void_p(w.data_ptr()) if w is not None else None,
-                                       C.c_size_t(src_idx.numel()), C.c_void_p(h.data_ptr()), C.c_size_t(h.shape[1]),
-                                       C.c_void_p(out.data_ptr()), st), "fgnn_block_aggregate")
+    n, dim = src_idx.numel(), h.shape[1]
+    if scaling is None:
+        code = L.fgnn_block_aggregate_ex(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, _ptr(h), dim, _ptr(out),
+                                         out.stride(0), _ptr(in_degree), _st(h))
+        what = "fgnn_block_aggregate_ex"
+    else:
+        src_deg, src_mode, dst_deg, dst_mode = scaling
+        code = L.fgnn_block_aggregate_scaled(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, _ptr(h), h.stride(0), dim,
+                                             _ptr(out), out.stride(0), _ptr(src_deg), src_mode, _ptr(dst_deg), dst_mode,
+                                             _st(h))
+        what = "fgnn_block_aggregate_scaled"
+    _lib._check(code, what)
+    return out
 
 
 class _BlockAggregate(torch.autograd.Function):
@@ -22,7 +43,7 @@ class _BlockAggregate(torch.autograd.Function):
     def forward(ctx, h, row, col, w, num_dst):
         h = h.contiguous()
         out = torch.zeros((num_dst, h.shape[1]), dtype=torch.float32, device=h.device)
-        _launch(row, col, w, h, out)
+        _aggregate(out, h, row, col, w)
         ctx.save_for_backward(row, col, w if w is not None else torch.empty(0, device=h.device))
         ctx.has_w = w is not None
         ctx.num_src = h.shape[0]
@@ -35,7 +56,7 @@ class _BlockAggregate(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             g = grad_out.contiguous()
             grad_h = torch.zeros((ctx.num_src, g.shape[1]), dtype=torch.float32, device=g.device)
-            _launch(col, row, w if ctx.has_w else None, g, grad_h)
+            _aggregate(grad_h, g, col, row, w if ctx.has_w else None)
         return grad_h, None, None, None, None
 
 
@@ -56,31 +77,18 @@ def aggregate_into(out, h, src_idx, dst_idx, edge_weight=None, in_degree=None):
     assert h.dtype == torch.float32 and out.dtype == torch.float32 and h.is_contiguous()
     assert out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
     assert src_idx.dtype == torch.int32 and dst_idx.dtype == torch.int32
-    L = _lib.load()
-    st = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
-    _lib._check(L.fgnn_block_aggregate_ex(
-        C.c_void_p(src_idx.data_ptr()), C.c_void_p(dst_idx.data_ptr()),
-        C.c_void_p(edge_weight.data_ptr()) if edge_weight is not None else None, C.c_size_t(src_idx.numel()),
-        C.c_void_p(h.data_ptr()), C.c_size_t(h.shape[1]), C.c_void_p(out.data_ptr()), C.c_size_t(out.stride(0)),
-        C.c_void_p(in_degree.data_ptr()) if in_degree is not None else None, st), "fgnn_block_aggregate_ex")
-    return out
+    return _aggregate(out, h, src_idx, dst_idx, edge_weight, in_degree)
 
 
 # ---- fused pieces of a GraphSAGE training step (csrc/train_ops.hip) ------------------------------------------------------
 # One launch each for work a step otherwise spends two to four torch ops on: the step is replayed as a captured HIP
 # graph (examples/graphed_step.py), where a node costs the GPU 15-20 us whatever it does.
 
-def _st(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def sage_finish_z(z, h, deg, num_dst, din):
     """z[:, :din] = h[:num_dst]; inv = 1 / max(deg, 1); z[:, din:] *= inv.  Returns inv (fp32 [num_dst])."""
     inv = torch.empty(num_dst, dtype=torch.float32, device=z.device)
-    _lib._check(_lib.load().fgnn_sage_finish_z(C.c_void_p(z.data_ptr()), C.c_size_t(z.stride(0)), C.c_void_p(h.data_ptr()),
-                                               C.c_size_t(h.stride(0)), C.c_void_p(deg.data_ptr()),
-                                               C.c_void_p(inv.data_ptr()), C.c_size_t(num_dst), C.c_size_t(din), _st(z)),
-                "fgnn_sage_finish_z")
+    _lib._check(_lib.load().fgnn_sage_finish_z(_ptr(z), z.stride(0), _ptr(h), h.stride(0), _ptr(deg), _ptr(inv), num_dst,
+                                               din, _st(z)), "fgnn_sage_finish_z")
     return inv
 
 
@@ -89,10 +97,8 @@ def sage_grad_prep(gz, inv, num_src, din):
     num_dst = gz.shape[0]
     gh = torch.empty((num_src, din), dtype=torch.float32, device=gz.device)
     gagg = torch.empty((num_dst, din), dtype=torch.float32, device=gz.device)
-    _lib._check(_lib.load().fgnn_sage_grad_prep(C.c_void_p(gz.data_ptr()), C.c_size_t(gz.stride(0)),
-                                                C.c_void_p(inv.data_ptr()), C.c_void_p(gh.data_ptr()),
-                                                C.c_void_p(gagg.data_ptr()), C.c_size_t(num_dst), C.c_size_t(num_src),
-                                                C.c_size_t(din), _st(gz)), "fgnn_sage_grad_prep")
+    _lib._check(_lib.load().fgnn_sage_grad_prep(_ptr(gz), gz.stride(0), _ptr(inv), _ptr(gh), _ptr(gagg), num_dst, num_src,
+                                                din, _st(gz)), "fgnn_sage_grad_prep")
     return gh, gagg
 
 
@@ -101,10 +107,8 @@ class _ReluDropout(torch.autograd.Function):
     def forward(ctx, x, p, seed, d_step, tag):
         x = x.contiguous()
         y = torch.empty_like(x)
-        _lib._check(_lib.load().fgnn_relu_dropout(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_size_t(x.numel()),
-                                                  C.c_float(p), C.c_uint64(seed),
-                                                  C.c_void_p(d_step.data_ptr()) if d_step is not None else None,
-                                                  C.c_uint32(tag), _st(x)), "fgnn_relu_dropout")
+        _lib._check(_lib.load().fgnn_relu_dropout(_ptr(x), _ptr(y), x.numel(), p, seed, _ptr(d_step), tag, _st(x)),
+                    "fgnn_relu_dropout")
         ctx.save_for_backward(y)
         ctx.p = p
         return y
@@ -114,9 +118,8 @@ class _ReluDropout(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         gy = gy.contiguous()
         gx = torch.empty_like(gy)
-        _lib._check(_lib.load().fgnn_relu_dropout_backward(C.c_void_p(y.data_ptr()), C.c_void_p(gy.data_ptr()),
-                                                           C.c_void_p(gx.data_ptr()), C.c_size_t(y.numel()),
-                                                           C.c_float(ctx.p), _st(y)), "fgnn_relu_dropout_backward")
+        _lib._check(_lib.load().fgnn_relu_dropout_backward(_ptr(y), _ptr(gy), _ptr(gx), y.numel(), ctx.p, _st(y)),
+                    "fgnn_relu_dropout_backward")
         return gx, None, None, None, None
 
 
@@ -132,11 +135,7 @@ def relu_dropout(x, p, training, seed=0x5A4D47, d_step=None, tag=0):
     return _ReluDropout.apply(x, float(p), int(seed), d_step, int(tag))
 
 
-# ---- fused GCN / PinSAGE layers (csrc/gnn_layers.hip) ----------------------------------------------------------------------
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
+# ---- fused GCN / PinSAGE layers (csrc/gnn_layers.hip; the scaled aggregation: csrc/block_aggregate.hip) -------------------
 
 def block_degrees(row, col, num_src, num_dst, edge_weight=None, want_src=True):
     """(src_deg or None, dst_deg), fp32, one launch over the edges: src_deg[row[e]] += 1 (GraphConv's out-degrees) and
@@ -148,8 +147,8 @@ def block_degrees(row, col, num_src, num_dst, edge_weight=None, want_src=True):
     # both vectors out of one zeroed buffer: one fill
     buf = torch.zeros((num_src if want_src else 0) + num_dst, dtype=torch.float32, device=col.device)
     src_deg, dst_deg = (buf[:num_src], buf[num_src:]) if want_src else (None, buf)
-    _lib._check(_lib.load().fgnn_block_degrees(_ptr(row), _ptr(col), _ptr(edge_weight), C.c_size_t(col.numel()),
-                                               _ptr(src_deg), _ptr(dst_deg), _st(col)), "fgnn_block_degrees")
+    _lib._check(_lib.load().fgnn_block_degrees(_ptr(row), _ptr(col), _ptr(edge_weight), col.numel(), _ptr(src_deg),
+                                               _ptr(dst_deg), _st(col)), "fgnn_block_degrees")
     return src_deg, dst_deg
 
 
@@ -164,11 +163,7 @@ def aggregate_scaled_into(out, h, src_idx, dst_idx, edge_weight=None, src_deg=No
     assert src_idx.is_contiguous() and dst_idx.is_contiguous() and src_idx.numel() == dst_idx.numel()
     for t in (edge_weight, src_deg, dst_deg):
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
-    _lib._check(_lib.load().fgnn_block_aggregate_scaled(
-        _ptr(src_idx), _ptr(dst_idx), _ptr(edge_weight), C.c_size_t(src_idx.numel()), _ptr(h), C.c_size_t(h.stride(0)),
-        C.c_size_t(h.shape[1]), _ptr(out), C.c_size_t(out.stride(0)), _ptr(src_deg), C.c_int(src_mode), _ptr(dst_deg),
-        C.c_int(dst_mode), _st(h)), "fgnn_block_aggregate_scaled")
-    return out
+    return _aggregate(out, h, src_idx, dst_idx, edge_weight, scaling=(src_deg, src_mode, dst_deg, dst_mode))
 
 
 class _ReluL2Norm(torch.autograd.Function):
@@ -177,8 +172,8 @@ class _ReluL2Norm(torch.autograd.Function):
         rows, dim = x.shape
         out = torch.empty((rows, dim), dtype=torch.float32, device=x.device)
         inv = torch.empty(rows, dtype=torch.float32, device=x.device)
-        _lib._check(_lib.load().fgnn_relu_l2norm(_ptr(x), C.c_size_t(x.stride(0)), _ptr(out), C.c_size_t(dim), _ptr(inv),
-                                                 C.c_size_t(rows), C.c_size_t(dim), _st(x)), "fgnn_relu_l2norm")
+        _lib._check(_lib.load().fgnn_relu_l2norm(_ptr(x), x.stride(0), _ptr(out), dim, _ptr(inv), rows, dim, _st(x)),
+                    "fgnn_relu_l2norm")
         ctx.save_for_backward(out, inv)
         return out
 
@@ -189,10 +184,8 @@ class _ReluL2Norm(torch.autograd.Function):
             gout = gout.contiguous()
         rows, dim = out.shape
         gx = torch.empty_like(out)
-        _lib._check(_lib.load().fgnn_relu_l2norm_backward(_ptr(out), C.c_size_t(dim), _ptr(inv), _ptr(gout),
-                                                          C.c_size_t(gout.stride(0)), _ptr(gx), C.c_size_t(dim),
-                                                          C.c_size_t(rows), C.c_size_t(dim), _st(out)),
-                    "fgnn_relu_l2norm_backward")
+        _lib._check(_lib.load().fgnn_relu_l2norm_backward(_ptr(out), dim, _ptr(inv), _ptr(gout), gout.stride(0), _ptr(gx),
+                                                          dim, rows, dim, _st(out)), "fgnn_relu_l2norm_backward")
         return gx
 
 
@@ -214,7 +207,7 @@ class _XentWs:
         key = (torch.device(device), n)
         ws = cls.cache.get(key)
         if ws is None:
-            nbytes = _lib.load().fgnn_softmax_xent_scratch_bytes(C.c_size_t(n))
+            nbytes = _lib.load().fgnn_softmax_xent_scratch_bytes(n)
             ws = cls.cache[key] = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=device)
         return ws
 
@@ -249,18 +242,14 @@ def softmax_xent(logits, labels, pad_rows=0):
     assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == logits.shape[0]
     n, c = logits.shape
-    L = _lib.load()
-    L.fgnn_softmax_xent_scratch_bytes.restype = C.c_size_t
     ws = _XentWs.get(logits.device, n)
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
     if pad_rows:
         g = xent_grad_buffer(logits.device, n + pad_rows, c)
     else:
         g = torch.empty((n, c), dtype=torch.float32, device=logits.device)
-    _lib._check(L.fgnn_softmax_xent(C.c_void_p(logits.data_ptr()), C.c_size_t(logits.stride(0)), C.c_void_p(labels.data_ptr()),
-                                    C.c_size_t(n), C.c_size_t(c), C.c_void_p(loss.data_ptr()), C.c_void_p(g.data_ptr()),
-                                    C.c_size_t(c), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel() * 4), _st(logits)),
-                "fgnn_softmax_xent")
+    _lib._check(_lib.load().fgnn_softmax_xent(_ptr(logits), logits.stride(0), _ptr(labels), n, c, _ptr(loss), _ptr(g), c,
+                                              _ptr(ws), ws.numel() * 4, _st(logits)), "fgnn_softmax_xent")
     return loss, g
 
 
@@ -299,10 +288,8 @@ class Adam:
             last = a + 8 >= len(live)
             cnt = self.step_count if last else self.step_count.clone()
             _lib._check(L.fgnn_adam_step(arr([p for p, _, _ in chunk]), arr(grads), arr([m for _, m, _ in chunk]),
-                                         arr([v for _, _, v in chunk]), numel, C.c_int(k), C.c_float(g["lr"]),
-                                         C.c_float(g["betas"][0]), C.c_float(g["betas"][1]), C.c_float(g["eps"]),
-                                         C.c_float(g["weight_decay"]), C.c_void_p(cnt.data_ptr()), _st(self.step_count)),
-                        "fgnn_adam_step")
+                                         arr([v for _, _, v in chunk]), numel, k, g["lr"], g["betas"][0], g["betas"][1],
+                                         g["eps"], g["weight_decay"], _ptr(cnt), _st(self.step_count)), "fgnn_adam_step")
 
     def state_dict(self):
         return {"step": int(self.step_count[0]), "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,

@@ -325,12 +325,16 @@ int fgnn_block_aggregate(const uint32_t *src_index, const uint32_t *dst_index, c
                          size_t num_edge, const float *h, size_t dim, float *out, void *stream);
 /* Same with a row stride for `out` (out_ld >= dim elements: the sums land in a column block of a wider matrix, e.g. the
  * right half of [h_dst | mean h_u]) and, if in_degree != NULL, in_degree[dst_index[e]] += 1 for every edge on the way
- * (float counts into a caller-zeroed array: the mean's denominators without a pass of their own). */
+ * (float counts into a caller-zeroed array: the mean's denominators without a pass of their own).
+ * Both functions check their arguments like fgnn_block_aggregate_scaled below: a null, zero-dim, short-leading-dimension
+ * or not 4-byte aligned argument, or a block of more than 2^31 - 1 workgroups (2^38 edges), returns FGNN_EINVAL before
+ * any launch. */
 int fgnn_block_aggregate_ex(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
                             size_t num_edge, const float *h, size_t dim, float *out, size_t out_ld, float *in_degree,
                             void *stream);
 
-/* ---- fused GCN / PinSAGE layers (csrc/gnn_layers.hip; examples/models.py FusedGraphConv, FusedWeightedSAGEConv) -------
+/* ---- fused GCN / PinSAGE layers (csrc/gnn_layers.hip, the scaled aggregation in csrc/block_aggregate.hip;
+ * examples/models.py FusedGraphConv, FusedWeightedSAGEConv) ------------------------------------------------------------
  * fp32, no host synchronisation, no allocation; a zero size returns FGNN_OK without a launch, a null, zero-dim,
  * short-leading-dimension or misaligned argument FGNN_EINVAL before any launch. */
 /* Both degree vectors of a block in one pass over the edges, into caller-zeroed arrays:

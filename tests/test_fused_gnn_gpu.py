@@ -170,7 +170,16 @@ def test_aggregate_scaled_refuses_bad_arguments_without_a_launch(hip, edges):
         aggregate_scaled_into(out, h, row, col, None, deg, 3, None, 0)
     with pytest.raises(hip.FgnnError):  # a mode without its degree vector
         aggregate_scaled_into(out, h, row, col, None, None, 1, None, 0)
+    # the plain entry points go through the same checks: a pointer that is not 4-byte aligned launches nothing
+    for where in range(5):
+        ptrs = [row.data_ptr(), col.data_ptr(), h.data_ptr(), out.data_ptr(), deg.data_ptr()]
+        ptrs[where] += 2
+        assert L.fgnn_block_aggregate_ex(C.c_void_p(ptrs[0]), C.c_void_p(ptrs[1]), None, C.c_size_t(E), C.c_void_p(ptrs[2]),
+                                         C.c_size_t(8), C.c_void_p(ptrs[3]), C.c_size_t(8), C.c_void_p(ptrs[4]), st) == -1
+    assert L.fgnn_block_aggregate(C.c_void_p(row.data_ptr()), C.c_void_p(col.data_ptr()), None, C.c_size_t(E),
+                                  C.c_void_p(h.data_ptr()), C.c_size_t(8), C.c_void_p(out.data_ptr() + 2), st) == -1
     torch.cuda.synchronize()
+    assert bool((deg == 1).all())
     assert not out.any()  # nothing was launched
     assert call() == 0 and bool(out.any())
     # a zero size is fine and launches nothing, whatever else is passed

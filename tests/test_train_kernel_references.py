@@ -93,6 +93,34 @@ def test_aggregation_cases_cover_what_they_claim():
     assert (col[128:192] == 250).all() and col[127] != 250 and col[192] != 250
 
 
+def test_single_flush_block_respects_the_chunk_rule_and_its_reference_the_bound():
+    """every destination owns one contiguous run, no run crosses a multiple of 32 in the edge array, run lengths 1 to 32
+    all occur, the last chunk is short and no multiple of 4; sequential_f32 on it lies inside aggregate_bound of
+    aggregate_ref (it is one of the orders the bound covers)"""
+    row, col, w = R.single_flush_block()
+    c = col.numpy()
+    heads = np.flatnonzero(np.r_[True, c[1:] != c[:-1]])
+    ends = np.r_[heads[1:], c.size]
+    assert len(set(c[heads].tolist())) == heads.size == len(R.EXACT_RUNS) < R.EXACT_NDST  # one run per destination
+    assert (ends - heads).tolist() == list(R.EXACT_RUNS) and set(R.EXACT_RUNS) == set(range(1, 33))
+    assert (heads // R.EXACT_CHUNK == (ends - 1) // R.EXACT_CHUNK).all()
+    assert 0 < c.size % R.EXACT_CHUNK and (c.size % R.EXACT_CHUNK) % 4 != 0
+    assert int(row.min()) == 0 and int(row.max()) == R.EXACT_NSRC - 1
+    assert bool((w != w.round()).all()) and float(w.min()) >= 0.25
+    for dim in (1, 65):
+        hbig, obig = R.exact_tensors(dim)
+        h, out0 = hbig[:, R.H_OFF:R.H_OFF + dim], obig[:, R.O_OFF:R.O_OFF + dim]
+        assert float(hbig.abs().min()) >= 0.25 and float(obig.abs().min()) >= 0.25
+        got = R.sequential_f32(row, col, w, h, out0)
+        assert got.dtype == np.float32
+        ref, S, k = R.aggregate_ref(row, col, w, h, R.EXACT_NDST, out0=out0)
+        R.assert_within(torch.from_numpy(got), ref, R.aggregate_bound(S, k), "sequential fp32, dim %d" % dim)
+        assert np.array_equal(got[k.numpy() == 0], out0.numpy()[k.numpy() == 0])
+        zero = R.sequential_f32(row, col, None, h, None)
+        ref, S, k = R.aggregate_ref(row, col, None, h, R.EXACT_NDST)
+        R.assert_within(torch.from_numpy(zero), ref, R.aggregate_bound(S, k), "sequential fp32 unweighted, dim %d" % dim)
+
+
 @pytest.mark.parametrize("dim", R.BACKWARD_DIMS)
 def test_fp32_aggregation_backward_stays_inside_the_derived_bound(dim):
     row, col, w, h, gout = R.backward_inputs(dim)

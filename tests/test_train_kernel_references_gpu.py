@@ -78,6 +78,40 @@ def test_aggregation_stays_inside_the_derived_bound(nn, case):
     assert torch.equal(out[(k == 0).cuda()], before[:, R.O_OFF:R.O_OFF + dim][(k == 0).cuda()])
 
 
+@pytest.mark.parametrize("dim", R.EXACT_DIMS)
+def test_aggregation_is_bit_exact_on_single_flush_blocks(nn, dim):
+    """train_refs.single_flush_block: every output element receives exactly one atomic add, so all three ways into the
+    aggregation kernel must equal sequential_f32 (products into the accumulator in edge order, one flush per segment,
+    then onto out0) bit for bit -- a reordered or fused accumulation inside a wave does not.  `out` enters non-zero as a
+    column block of a wider matrix, the scaled call reads h out of a wider matrix too; the in-degrees equal bincount."""
+    row, col, w = R.single_flush_block()
+    hbig, obig = R.exact_tensors(dim)
+    h_cpu, out0 = hbig[:, R.H_OFF:R.H_OFF + dim], obig[:, R.O_OFF:R.O_OFF + dim]
+    want = R.sequential_f32(row, col, w, h_cpu, out0).view(np.int32)
+    drow, dcol, dw, dh = row.cuda(), col.cuda(), w.cuda(), hbig.cuda()
+    h = dh[:, R.H_OFF:R.H_OFF + dim]
+
+    def bits(t):
+        return t.cpu().contiguous().numpy().view(np.int32)
+
+    big = obig.cuda()
+    deg = torch.zeros(R.EXACT_NDST, device="cuda")
+    nn.aggregate_into(big[:, R.O_OFF:R.O_OFF + dim], h.contiguous(), drow, dcol, dw, in_degree=deg)
+    assert np.array_equal(bits(big[:, R.O_OFF:R.O_OFF + dim]), want)
+    assert torch.equal(deg.cpu(), torch.bincount(col.long(), minlength=R.EXACT_NDST).float())
+    keep = torch.ones(dim + R.O_PAD, dtype=torch.bool)
+    keep[R.O_OFF:R.O_OFF + dim] = False
+    assert np.array_equal(bits(big[:, keep.cuda()]), bits(obig[:, keep]))
+
+    big = obig.cuda()
+    nn.aggregate_scaled_into(big[:, R.O_OFF:R.O_OFF + dim], h, drow, dcol, dw, None, 0, None, 0)
+    assert np.array_equal(bits(big[:, R.O_OFF:R.O_OFF + dim]), want)
+    assert np.array_equal(bits(big[:, keep.cuda()]), bits(obig[:, keep]))
+
+    got = nn.block_aggregate(h.contiguous(), drow, dcol, R.EXACT_NDST, edge_weight=dw)
+    assert np.array_equal(bits(got), R.sequential_f32(row, col, w, h_cpu, None).view(np.int32))
+
+
 @pytest.mark.parametrize("dim", R.BACKWARD_DIMS)
 def test_block_aggregate_backward_is_the_reference_with_the_roles_swapped(nn, dim):
     """_BlockAggregate under autograd: the output against aggregate_ref, the input gradient against aggregate_ref with

@@ -246,9 +246,59 @@ def backward_inputs(dim):
     return row, col, w, torch.randn((NSRC, dim), generator=g), torch.randn((NDST, dim), generator=g)
 
 
+# ---- bit-exact aggregation on single-flush blocks ------------------------------------------------------------------------
+# A block in which every destination owns ONE run of edges and no run crosses a multiple of 32 in the edge array (the
+# kernel's chunk per wave): every output element then receives exactly one atomic add, so the result does not depend on
+# any order between waves and equals a sequential fp32 computation.  The derived bound above cannot tell a reordered
+# accumulation inside a wave from the original; equality with sequential_f32 can.
+
+EXACT_DIMS = (1, 64, 65, 128, 129, 257, 600)
+EXACT_NSRC, EXACT_NDST = 40, 40
+EXACT_CHUNK = 32
+# chunk by chunk: one run of 32, (k, 32 - k) for k = 1 .. 15, (16, 16), and a last chunk of 13 edges (not a multiple of
+# the edge loop's unroll of 4, so its last trip runs on clamped lanes)
+EXACT_RUNS = (32,) + tuple(n for k in range(1, 16) for n in (k, 32 - k)) + (16, 16) + (5, 1, 7)
+
+
+@functools.lru_cache(maxsize=None)
+def single_flush_block():
+    """(row int32 [E], col int32 [E], w fp32 [E]) as CPU tensors: runs of EXACT_RUNS edges, each to a destination of its
+    own (36 of the 40, in scattered order), sources drawn from all 40, non-integer weights in [0.25, 1.5)"""
+    rs = np.random.default_rng(4242)
+    dst = rs.permutation(EXACT_NDST)[:len(EXACT_RUNS)]
+    col = np.repeat(dst, EXACT_RUNS)
+    row = rs.integers(0, EXACT_NSRC, col.size)
+    w = (0.25 + 1.25 * rs.random(col.size)).astype(np.float32)
+    t = torch.from_numpy
+    return t(row.astype(np.int32)), t(col.astype(np.int32)), t(w)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_tensors(dim):
+    """(hbig fp32 [40, dim + 13], obig fp32 [40, dim + 24]) with h = columns 5 .. 5 + dim and the output block = columns
+    8 .. 8 + dim (H_OFF, O_OFF); magnitudes in [0.25, 2) with random signs: no product or sum comes near a denormal"""
+    rs = np.random.default_rng(9000 + dim)
+
+    def draw(shape):
+        return ((0.25 + 1.75 * rs.random(shape)) * rs.choice([-1.0, 1.0], shape)).astype(np.float32)
+    return torch.from_numpy(draw((EXACT_NSRC, dim + H_PAD))), torch.from_numpy(draw((EXACT_NDST, dim + O_PAD)))
+
+
+def sequential_f32(row, col, w, h, out0):
+    """fp32 [num_dst, dim] (numpy): acc = 0; for each edge in order acc = f32(acc + f32(w * h)); out = f32(out0 + acc),
+    every operation rounded to fp32 on its own (no fused multiply-add).  w None: weight 1, out0 None: zeros."""
+    row, col, h = np.asarray(row), np.asarray(col), np.asarray(h, dtype=np.float32)
+    acc = np.zeros((EXACT_NDST, h.shape[1]), dtype=np.float32)
+    for e in range(row.size):
+        term = h[row[e]] if w is None else np.float32(w[e]) * h[row[e]]
+        acc[col[e]] = acc[col[e]] + term
+    assert acc.dtype == np.float32
+    return acc if out0 is None else np.asarray(out0, dtype=np.float32) + acc
+
+
 # ---- softmax cross entropy -----------------------------------------------------------------------------------------------
 
-XENT_C = (1, 2, 64, 65, 255, 256, 257, 1000)
+XENT_C =(1, 2, 64, 65, 255, 256, 257, 1000)
 XENT_N = (1, 5, 2500)
 
 

@@ -24,9 +24,16 @@ ap.add_argument("--fused", type=int, default=None, choices=[0, 1],
 ap.add_argument("--ab", type=int, default=5, help="gcn / pinsage: alternations of the op-by-op and the fused model")
 ap.add_argument("--ab-steps", type=int, default=50)
 ap.add_argument("--workload", default=None, help="gcn / pinsage: bench.py workload the batch comes from")
+ap.add_argument("--kernel-lib", default=None, metavar="PATH",
+                help="another build of libfgnn_hip.so to bind (lib.use_library), e.g. an earlier commit's: the C ABI is "
+                     "the yardstick, so one Python tree times either build")
 args = ap.parse_args()
 if args.fused is not None:
     os.environ["SAGE_FUSED"] = str(args.fused)
+if args.kernel_lib:
+    from fgnn_hip import lib as _kernel_lib
+    _kernel_lib.use_library(args.kernel_lib)
+    print("kernel library: %s" % _kernel_lib.LIB_PATH)
 
 
 def real_batch_blocks(workload, dev):
