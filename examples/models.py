@@ -355,6 +355,138 @@ class FusedWeightedSAGEConv(WeightedSAGEConv):
         return relu_l2norm(self.W(self.dropout(z)))
 
 
+class GATConv(nn.Module):
+    """dgl.nn.GATConv on a block as the reference's GAT uses it (example/samgraph/train_gat.py), op by op: one `fc` for
+    sources and destinations (feat_dst = feat_src[:num_dst]), additive attention el[u] + er[v] through LeakyReLU,
+    softmax over every destination's incoming edges per head, attention dropout, weighted sum, residual, bias,
+    activation.  A destination without an edge gets residual + bias only (allow_zero_in_degree=True).  Parameter names
+    and shapes are DGL's (fc.weight, attn_l / attn_r [1, H, F], bias [H F], res_fc.weight when the residual needs a
+    projection), so the reference's checkpoints load.  Returns [num_dst, H, F]."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False,
+                 activation=None):
+        super().__init__()
+        self.in_feats, self.out_feats, self.num_heads = in_feats, out_feats, num_heads
+        self.fc = TallLinear(in_feats, out_feats * num_heads, bias=False)
+        self.attn_l = nn.Parameter(th.empty(1, num_heads, out_feats))
+        self.attn_r = nn.Parameter(th.empty(1, num_heads, out_feats))
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.negative_slope = negative_slope
+        self.res_fc = None
+        if residual:
+            self.res_fc = (TallLinear(in_feats, out_feats * num_heads, bias=False) if in_feats != out_feats * num_heads
+                           else nn.Identity())
+        self.bias = nn.Parameter(th.zeros(num_heads * out_feats))
+        self.activation = activation
+        gain = nn.init.calculate_gain("relu")  # DGL's reset_parameters
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_l, gain=gain)
+        nn.init.xavier_normal_(self.attn_r, gain=gain)
+        if isinstance(self.res_fc, nn.Linear):
+            nn.init.xavier_normal_(self.res_fc.weight, gain=gain)
+
+    def project(self, block, h):
+        """(h_dst after feature dropout, feat_src [num_src, H, F], el [num_src, H], er [num_dst, H])"""
+        num_dst = block.number_of_dst_nodes()
+        h = self.feat_drop(h)
+        feat = self.fc(h).view(-1, self.num_heads, self.out_feats)
+        el = (feat * self.attn_l).sum(-1)
+        er = (feat[:num_dst] * self.attn_r).sum(-1)
+        return h[:num_dst], feat, el, er
+
+    def finish(self, rst, h_dst, biased=False):
+        """residual, bias (unless it is in rst already) and activation"""
+        if self.res_fc is not None and not biased:
+            rst = rst + self.res_fc(h_dst).view(h_dst.shape[0], -1, self.out_feats)
+        if not biased:
+            rst = rst + self.bias.view(1, self.num_heads, self.out_feats)
+        return self.activation(rst) if self.activation else rst
+
+    def forward(self, block, h):
+        num_dst = block.number_of_dst_nodes()
+        h_dst, feat, el, er = self.project(block, h)
+        row, col = block.row.long(), block.col.long()
+        e = F.leaky_relu(el[row] + er[col], self.negative_slope)  # [E, H]
+        # edge softmax: per (destination, head) max, exp, sum -- destinations without an edge are never indexed
+        m = th.full((num_dst, self.num_heads), float("-inf"), dtype=e.dtype, device=e.device)
+        # (the max only guards exp against overflow, the softmax does not depend on it: no gradient through it)
+        m = m.scatter_reduce(0, col.unsqueeze(1).expand_as(e), e.detach(), reduce="amax", include_self=True)
+        p = th.exp(e - m[col])
+        z = th.zeros((num_dst, self.num_heads), dtype=e.dtype, device=e.device).index_add_(0, col, p)
+        a = self.attn_drop(p / z[col])
+        rst = th.zeros((num_dst, self.num_heads, self.out_feats), dtype=feat.dtype, device=feat.device)
+        rst = rst.index_add_(0, col, feat[row] * a.unsqueeze(-1))
+        return self.finish(rst, h_dst)
+
+
+class FusedGATConv(GATConv):
+    """GATConv with everything between the projections and the activation -- scores, edge softmax, attention dropout,
+    aggregation -- as one autograd node on the kernels of csrc/gat_attention.hip (fgnn_hip.nn.gat_attention): no E x H x
+    F tensor is written in either direction.  The bias (and the residual) is pre-filled into the node's output, which
+    the kernel accumulates into.  Same parameters under the same names; off the GPU / without the HIP library / for
+    other dtypes it IS GATConv.  `dropout_key` = (seed, d_step, tag) of the attention mask, set by the model before
+    every forward."""
+
+    dropout_key = (0x5A4D47, None, 0)
+
+    def forward(self, block, h):
+        if not _fused_layers_apply(block, h):
+            return super().forward(block, h)
+        from fgnn_hip.nn import gat_attention
+        num_dst = block.number_of_dst_nodes()
+        h_dst, feat, el, er = self.project(block, h)
+        bias = self.bias.view(1, self.num_heads, self.out_feats)
+        if self.res_fc is not None:
+            out = self.res_fc(h_dst).view(num_dst, self.num_heads, self.out_feats) + bias
+        else:
+            out = bias.expand(num_dst, -1, -1).contiguous()
+        seed, d_step, tag = self.dropout_key
+        rst = gat_attention(feat, el, er, block.row, block.col, num_dst, self.negative_slope, self.attn_drop.p,
+                            self.training, seed, d_step, tag, out=out)
+        return self.finish(rst, h_dst, biased=True)
+
+
+class GAT(nn.Module):
+    """the reference's GAT (example/samgraph/train_gat.py): inner layers of `heads` heads with n_hidden // heads
+    features each, flattened (layer width n_hidden: 256 = 8 x 32), ELU; the last layer `out_heads` heads of n_classes,
+    averaged.  Feature dropout `dropout` and attention dropout `attn_drop` (default: the same) in every layer."""
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True, heads=8, out_heads=1,
+                 attn_drop=None, negative_slope=0.2, residual=False):
+        super().__init__()
+        assert n_hidden % heads == 0, "n_hidden must be a multiple of heads"
+        attn_drop = dropout if attn_drop is None else attn_drop
+        conv = FusedGATConv if fused else GATConv
+        self.fused = fused
+        layers = []
+        for i in range(n_layers):
+            last = i == n_layers - 1
+            layers.append(conv(in_feats if i == 0 else n_hidden, n_classes if last else n_hidden // heads,
+                               out_heads if last else heads, dropout, attn_drop, negative_slope,
+                               residual and i > 0, None if last else F.elu))
+        self.layers = nn.ModuleList(layers)
+        # as SAGE / GCN: a training loop that uses fgnn_hip.nn.Adam sets dropout_step to its device-side step count, which
+        # then keys the attention masks (a replayed graph draws a fresh mask per step).  Unset: every forward takes a fresh
+        # seed from a host-side counter (no device synchronisation; a captured forward replays ITS mask)
+        self.dropout_step = None
+        self.dropout_seed = 0x5A4D47
+        self._host_draws = 0
+
+    def forward(self, blocks, x):
+        seed = self.dropout_seed
+        if self.fused and self.dropout_step is None and self.training:
+            self._host_draws += 1
+            seed = (seed + 0x9E3779B97F4A7C15 * self._host_draws) & 0xFFFFFFFFFFFFFFFF
+        h = x
+        for i, (layer, block) in enumerate(zip(self.layers, blocks)):
+            if self.fused:
+                layer.dropout_key = (seed, self.dropout_step, i)
+            h = layer(block, h)
+            h = h.mean(1) if i == len(self.layers) - 1 else h.flatten(1)
+        return h
+
+
 class SAGE(nn.Module):
     def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True):
         super().__init__()
@@ -431,4 +563,4 @@ class PinSAGE(nn.Module):
         return h
 
 
-MODELS = {"graphsage": SAGE, "gcn": GCN, "pinsage": PinSAGE}
+MODELS = {"graphsage": SAGE, "gcn": GCN, "pinsage": PinSAGE, "gat": GAT}

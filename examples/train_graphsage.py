@@ -62,6 +62,9 @@ def main():
                     help="validation accuracy every N steps and test accuracy at the end (the reference's --report-acc, "
                          "multi_gpu/train_graphsage.py:65,344-347,395-397); 0: off")
     ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
+    # GAT (example/samgraph/train_gat.py: 8 heads x 32 hidden, attention dropout = feature dropout)
+    ap.add_argument("--num-heads", type=int, default=8, help="gat: attention heads of the inner layers")
+    ap.add_argument("--attn-drop", type=float, default=None, help="gat: attention dropout (default: --dropout)")
     ap.add_argument("--cache-policy", default="pre_sample",
                     help="a key of sam.cache_policies: pre_sample, presample_static, degree, ..., or dynamic_cache "
                          "(arch4 only: the cache is the previous batch's feature tensor; khop0 / khop1 / weighted_khop, "
@@ -104,8 +107,9 @@ def main():
         sam.start()
     dev = th.device(trainer_ctx)
     num_layer = args.num_layer if args.model == "pinsage" else len(args.fanout)
+    kw = dict(heads=args.num_heads, attn_drop=args.attn_drop) if args.model == "gat" else {}
     model = MODELS[args.model](sam.feat_dim(), args.num_hidden, sam.num_class(), num_layer, args.dropout,
-                               fused=not args.op_by_op).to(dev)
+                               fused=not args.op_by_op, **kw).to(dev)
     get_blocks = sam.get_dgl_blocks_with_weights if args.model == "pinsage" else sam.get_dgl_blocks
     accuracy = None
     if args.report_acc and args.model != "pinsage":

@@ -47,6 +47,7 @@ EXPORTS = [
     "fgnn_sage_finish_z", "fgnn_sage_grad_prep", "fgnn_relu_dropout", "fgnn_relu_dropout_backward",
     "fgnn_softmax_xent_scratch_bytes", "fgnn_softmax_xent", "fgnn_adam_step",
     "fgnn_block_degrees", "fgnn_block_aggregate_scaled", "fgnn_relu_l2norm", "fgnn_relu_l2norm_backward",
+    "fgnn_gat_workspace_bytes", "fgnn_gat_forward", "fgnn_gat_backward",
 ]
 
 _lib = None
@@ -62,6 +63,11 @@ _TRAIN_SIGNATURES = {
     "fgnn_block_degrees": (_I, [_P, _P, _P, _Z, _P, _P, _P]),
     "fgnn_relu_l2norm": (_I, [_P, _Z, _P, _Z, _P, _Z, _Z, _P]),
     "fgnn_relu_l2norm_backward": (_I, [_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P]),
+    "fgnn_gat_workspace_bytes": (_Z, [_Z, _Z, _Z]),
+    "fgnn_gat_forward": (_I, [_P, _P, _Z, _P, _P, _P, _Z, _Z, _Z, _Z, _F, _F, C.c_uint64, _P, C.c_uint32, _P, _P, _Z, _P,
+                              _Z, _P]),
+    "fgnn_gat_backward": (_I, [_P, _P, _Z, _P, _P, _P, _Z, _P, _P, _Z, _Z, _Z, _Z, _F, _F, C.c_uint64, _P, C.c_uint32, _P,
+                               _Z, _P, _P, _P, _Z, _P]),
     "fgnn_sage_finish_z": (_I, [_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P]),
     "fgnn_sage_grad_prep": (_I, [_P, _Z, _P, _P, _P, _Z, _Z, _Z, _P]),
     "fgnn_relu_dropout": (_I, [_P, _P, _Z, _F, C.c_uint64, _P, C.c_uint32, _P]),

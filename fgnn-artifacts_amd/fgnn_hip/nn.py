@@ -198,6 +198,117 @@ def relu_l2norm(x):
     return _ReluL2Norm.apply(x)
 
 
+# ---- fused GAT layer: edge-softmax attention + aggregation (csrc/gat_attention.hip) ---------------------------------------
+
+_GAT_WS = {}
+
+
+def gat_workspace(device, num_edge, num_dst, num_head):
+    """the scratch of fgnn_gat_forward / fgnn_gat_backward for these sizes on `device` (per-destination max and sums,
+    per-edge scores), cached per (device, sizes): call it BEFORE a graph capture whose first gat_attention call would
+    otherwise allocate it inside the capture.  Neither call expects anything of its contents."""
+    key = (torch.device(device), num_edge, num_dst, num_head)
+    ws = _GAT_WS.get(key)
+    if ws is None:
+        nbytes = _lib.load().fgnn_gat_workspace_bytes(num_edge, num_dst, num_head)
+        ws = _GAT_WS[key] = torch.empty(max((nbytes + 3) // 4, 1), dtype=torch.float32, device=device)
+    return ws
+
+
+def _rows_ok(t):
+    """[rows, H, F] fp32 with unit strides inside a row (a column block of a wider matrix is fine)"""
+    return t.dtype == torch.float32 and t.dim() == 3 and t.stride(2) == 1 and t.stride(1) == t.shape[2] \
+        and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1] * t.shape[2])
+
+
+def gat_forward_into(out, alpha, feat, el, er, row, col, negative_slope=0.2, attn_p=0.0, seed=0, d_step=None, tag=0):
+    """fgnn_gat_forward, no autograd: alpha [E, H] is written, the attention-weighted sums are ADDED to the
+    caller-initialised out [num_dst, H, F] (out and feat may be column blocks of wider matrices)"""
+    num_dst, H, F = out.shape
+    assert _rows_ok(out) and _rows_ok(feat) and feat.shape[1:] == out.shape[1:]
+    assert el.dtype == torch.float32 and el.is_contiguous() and el.shape == (feat.shape[0], H)
+    assert er.dtype == torch.float32 and er.is_contiguous() and er.shape == (num_dst, H)
+    assert row.dtype == torch.int32 and col.dtype == torch.int32 and row.is_contiguous() and col.is_contiguous()
+    assert row.numel() == col.numel() and alpha.dtype == torch.float32 and alpha.is_contiguous()
+    assert alpha.shape == (row.numel(), H)
+    E = row.numel()
+    ws = gat_workspace(feat.device, E, num_dst, H)
+    _lib._check(_lib.load().fgnn_gat_forward(_ptr(row), _ptr(col), E, _ptr(el), _ptr(er), _ptr(feat), feat.stride(0),
+                                             num_dst, H, F, negative_slope, attn_p, seed, _ptr(d_step), tag, _ptr(alpha),
+                                             _ptr(out), out.stride(0), _ptr(ws), ws.numel() * 4, _st(feat)),
+                "fgnn_gat_forward")
+    return out
+
+
+def gat_backward_into(gfeat, gel, ger, gout, alpha, feat, el, er, row, col, negative_slope=0.2, attn_p=0.0, seed=0,
+                      d_step=None, tag=0):
+    """fgnn_gat_backward, no autograd: the gradients are ADDED to the caller-initialised gfeat [num_src, H, F], gel
+    [num_src, H] and ger [num_dst, H]; each may be None and is then skipped.  The dropout key is the forward call's."""
+    num_dst, H, F = gout.shape
+    assert _rows_ok(gout) and _rows_ok(feat) and feat.shape[1:] == gout.shape[1:]
+    assert gfeat is None or (_rows_ok(gfeat) and gfeat.shape == feat.shape)
+    for t, n in ((el, feat.shape[0]), (er, num_dst), (gel, feat.shape[0]), (ger, num_dst), (alpha, row.numel())):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == (n, H))
+    assert row.dtype == torch.int32 and col.dtype == torch.int32 and row.is_contiguous() and col.is_contiguous()
+    assert row.numel() == col.numel()
+    E = row.numel()
+    ws = gat_workspace(feat.device, E, num_dst, H)
+    _lib._check(_lib.load().fgnn_gat_backward(_ptr(row), _ptr(col), E, _ptr(el), _ptr(er), _ptr(feat), feat.stride(0),
+                                              _ptr(alpha), _ptr(gout), gout.stride(0), num_dst, H, F, negative_slope,
+                                              attn_p, seed, _ptr(d_step), tag, _ptr(gfeat),
+                                              gfeat.stride(0) if gfeat is not None else 0, _ptr(gel), _ptr(ger), _ptr(ws),
+                                              ws.numel() * 4, _st(feat)), "fgnn_gat_backward")
+
+
+class _GatAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, el, er, out, row, col, slope, attn_p, seed, d_step, tag):
+        el, er = el.contiguous(), er.contiguous()
+        if not _rows_ok(feat):
+            feat = feat.contiguous()
+        ctx.mark_dirty(out)
+        alpha = torch.empty((row.numel(), feat.shape[1]), dtype=torch.float32, device=feat.device)
+        gat_forward_into(out, alpha, feat, el, er, row, col, slope, attn_p, seed, d_step, tag)
+        ctx.save_for_backward(feat, el, er, alpha, row, col)
+        ctx.key = (slope, attn_p, seed, d_step, tag)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        feat, el, er, alpha, row, col = ctx.saved_tensors
+        if not _rows_ok(gout):
+            gout = gout.contiguous()
+        want = ctx.needs_input_grad
+        gfeat, gel, ger = (torch.zeros_like(t, memory_format=torch.contiguous_format) if w else None
+                           for t, w in zip((feat, el, er), want[:3]))
+        if any(want[:3]):
+            gat_backward_into(gfeat, gel, ger, gout, alpha, feat, el, er, row, col, *ctx.key)
+        return gfeat, gel, ger, (gout if want[3] else None), None, None, None, None, None, None, None
+
+
+def gat_attention(feat, el, er, row, col, num_dst, negative_slope=0.2, attn_drop=0.0, training=False, seed=0x5A4D47,
+                  d_step=None, tag=0, out=None):
+    """GAT's message passing on a block as one autograd node, differentiable in feat, el and er:
+        a = edge_softmax(leaky_relu(el[row] + er[col], negative_slope)) per destination and head
+        out[col[e], h, :] += dropout(a, attn_drop)[e, h] * feat[row[e], h, :]
+    feat fp32 [num_src, H, F], el [num_src, H], er [num_dst, H], row / col int32 [E].  Returns [num_dst, H, F]: `out` if
+    given -- a contiguous fp32 tensor that already holds what the sums are added to (a bias, a residual; gradients flow
+    into it unchanged) and is modified in place -- else a new tensor.  The dropout mask (training and attn_drop > 0) comes
+    from Philox keyed (seed, *d_step, tag, e H + h), see relu_dropout; the backward pass regenerates it."""
+    assert feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 3
+    H, F = feat.shape[1], feat.shape[2]
+    assert el.dtype == torch.float32 and er.dtype == torch.float32
+    assert el.shape == (feat.shape[0], H) and er.shape == (num_dst, H)
+    assert row.dtype == torch.int32 and col.dtype == torch.int32
+    assert row.is_contiguous() and col.is_contiguous() and row.numel() == col.numel()
+    assert 0.0 <= attn_drop < 1.0
+    if out is None:
+        out = torch.zeros((num_dst, H, F), dtype=torch.float32, device=feat.device)
+    assert out.dtype == torch.float32 and out.shape == (num_dst, H, F) and out.is_contiguous()
+    p = float(attn_drop) if training else 0.0
+    return _GatAttention.apply(feat, el, er, out, row, col, float(negative_slope), p, int(seed), d_step, int(tag))
+
+
 class _XentWs:
     """scratch of fgnn_softmax_xent per (device, n): arrival counter (zeroed once) + row losses"""
     cache = {}

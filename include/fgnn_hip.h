@@ -358,6 +358,42 @@ int fgnn_relu_l2norm(const float *x, size_t x_ld, float *out, size_t out_ld, flo
 int fgnn_relu_l2norm_backward(const float *out, size_t out_ld, const float *inv_norm, const float *gout, size_t gout_ld,
                               float *gx, size_t gx_ld, size_t rows, size_t dim, void *stream);
 
+/* ---- fused GAT layer: edge-softmax attention and its aggregation (csrc/gat_attention.hip; examples/models.py
+ * FusedGATConv; reference: dgl.nn.GATConv of example/samgraph/train_gat.py) ------------------------------------------------
+ * num_head heads H of num_feat features F each; feat / out / gout / gfeat are [rows, H, F] with a row stride (>= H F
+ * elements), el [num_src, H], er [num_dst, H], alpha [num_edge, H], all fp32 and 4-byte aligned.
+ *   s[e,h] = leaky_relu(el[src_index[e],h] + er[dst_index[e],h], negative_slope)
+ *   alpha[e,h] = exp(s[e,h] - m) / sum over the edges with the same dst_index of exp(s - m),  m = their max of s
+ *   a~[e,h] = alpha[e,h] * keep[e,h] / (1 - attn_p)         keep: the Philox mask of fgnn_relu_dropout keyed (seed,
+ *                                                           *d_step (NULL: 0), tag), element e H + h; attn_p == 0: none
+ *   out[dst_index[e],h,:] += a~[e,h] * feat[src_index[e],h,:]
+ * Any edge order gives the same result up to the order of the float additions; contiguous equal dst_index values (the
+ * samplers' seed-major order) are the fast case.  Nothing of size num_edge x H x F is written.  No host
+ * synchronisation, no allocation: all launches are enqueued on `stream`.  num_edge == 0 returns FGNN_OK and touches
+ * nothing; a destination without an edge keeps its out row.  FGNN_EINVAL before any launch: a null required pointer,
+ * num_head or num_feat 0, a row stride below H F, a pointer that is not 4-byte aligned, attn_p outside [0, 1), ws_bytes
+ * below fgnn_gat_workspace_bytes(num_edge, num_dst, num_head). */
+size_t fgnn_gat_workspace_bytes(size_t num_edge, size_t num_dst, size_t num_head);
+/* alpha (written: the normalised attention BEFORE dropout, kept for the backward pass) and out (caller-initialised:
+ * a bias or a residual may already be in it).  In eval mode pass attn_p = 0. */
+int fgnn_gat_forward(const uint32_t *src_index, const uint32_t *dst_index, size_t num_edge, const float *el,
+                     const float *er, const float *feat, size_t feat_ld, size_t num_dst, size_t num_head,
+                     size_t num_feat, float negative_slope, float attn_p, uint64_t seed,
+                     const unsigned long long *d_step, uint32_t tag, float *alpha, float *out, size_t out_ld, void *ws,
+                     size_t ws_bytes, void *stream);
+/* With g = gout and the same dropout key as the forward call (the mask is regenerated):
+ *   gfeat[src_index[e],h,:] += a~[e,h] * g[dst_index[e],h,:]
+ *   ga[e,h] = <g[dst_index[e],h,:], feat[src_index[e],h,:]> * keep[e,h] / (1 - attn_p)
+ *   gs[e,h] = alpha[e,h] * (ga[e,h] - sum over the edges with the same dst_index of alpha * ga)
+ *   gel[src_index[e],h] += gs[e,h] * (el + er > 0 ? 1 : negative_slope),  ger[dst_index[e],h] += the same
+ * gfeat (row stride gfeat_ld), gel and ger are caller-initialised accumulators; each may be NULL and is then skipped.
+ * The workspace need not be the forward call's, nor keep its contents in between. */
+int fgnn_gat_backward(const uint32_t *src_index, const uint32_t *dst_index, size_t num_edge, const float *el,
+                      const float *er, const float *feat, size_t feat_ld, const float *alpha, const float *gout,
+                      size_t gout_ld, size_t num_dst, size_t num_head, size_t num_feat, float negative_slope,
+                      float attn_p, uint64_t seed, const unsigned long long *d_step, uint32_t tag, float *gfeat,
+                      size_t gfeat_ld, float *gel, float *ger, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- fused pieces of a GraphSAGE training step (consumer side, csrc/train_ops.hip) ----------------------------------
  * Elementwise work a training step otherwise does with two to four framework ops each; one launch apiece because the
  * step is replayed as a captured HIP graph, where every node costs the GPU 15-20 us whatever it does.  fp32, the same

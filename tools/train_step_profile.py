@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where does a training step (the layers of examples/models.py on the engine's COO blocks) spend GPU time?
-Default (--model graphsage): synthetic blocks of the papers100M-shaped batch size.  --model gcn / pinsage: the blocks
-of one real batch of bench.py's twitter / uk-2006-05 workload (same graph, train set and sampler), the op-by-op and the
+Default (--model graphsage): synthetic blocks of the papers100M-shaped batch size.  --model gcn / pinsage / gat: the blocks
+of one real batch of bench.py's twitter / uk-2006-05 / products workload (same graph, train set and sampler), the op-by-op and the
 fused model stepped in alternation in this process (--ab alternations of --ab-steps steps, medians and spread per
 model), then the per-kernel table of the --fused one.  Profiling aid."""
 import argparse
@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "fgnn-artifacts_amd"))
 from models import MODELS, SAGE  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--model", default="graphsage", choices=["graphsage", "gcn", "pinsage"])
+ap.add_argument("--model", default="graphsage", choices=["graphsage", "gcn", "pinsage", "gat"])
 ap.add_argument("--fused", type=int, default=None, choices=[0, 1],
                 help="the fused layers (1) or the op-by-op ones (0); default 1 (graphsage: SAGE_FUSED)")
 ap.add_argument("--ab", type=int, default=5, help="gcn / pinsage: alternations of the op-by-op and the fused model")
@@ -74,7 +74,7 @@ def ab_main():
     from fgnn_hip.nn import Adam, softmax_xent
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    workload = args.workload or {"gcn": "twitter", "pinsage": "uk-2006-05"}[args.model]
+    workload = args.workload or {"gcn": "twitter", "pinsage": "uk-2006-05", "gat": "products"}[args.model]
     blocks, w = real_batch_blocks(workload, dev)
     print("%s batch of %s: %s" % (args.model, workload, ", ".join(
         "%d src -> %d dst, %d edges" % (b.nsrc, b.ndst, b.row.numel()) for b in blocks)))
