@@ -31,10 +31,33 @@ unsigned long long *scan_help_counter() {
 }
 static std::atomic<int> g_scan_help_after{-1};
 int scan_help_after_override() { return g_scan_help_after.load(std::memory_order_relaxed); }
+// fgnn_debug_set_stateless_ticket_start_once: bit 32 = armed
+static std::atomic<unsigned long long> g_stateless_ticket_start{0};
+bool take_stateless_ticket_start(uint32_t *start) {
+  if (g_stateless_ticket_start.load(std::memory_order_relaxed) == 0) return false;
+  const unsigned long long v = g_stateless_ticket_start.exchange(0, std::memory_order_relaxed);
+  *start = (uint32_t)v;
+  return v != 0;
+}
 }  // namespace fgnn
 
 extern "C" void fgnn_debug_set_scan_help_after(int polls) {
   fgnn::g_scan_help_after.store(polls, std::memory_order_relaxed);
+}
+
+extern "C" void fgnn_debug_set_stateless_ticket_start_once(uint32_t start) {
+  fgnn::g_stateless_ticket_start.store((1ull << 32) | start, std::memory_order_relaxed);
+}
+
+extern "C" int fgnn_debug_scan_block_sums(uint32_t *d_sums, size_t n, size_t *d_total64, uint32_t *d_total32,
+                                          const uint32_t *d_accum, uint32_t *d_accum_out, const uint32_t *d_items32,
+                                          const size_t *d_items64, uint32_t items_per_sum, void *stream) {
+  if (n && !d_sums) return FGNN_EINVAL;
+  auto st = static_cast<hipStream_t>(stream);
+  int rc = fgnn::launch_scan_block_sums(d_sums, n, d_total64, d_total32, d_accum, d_accum_out, st, d_items32,
+                                        items_per_sum, d_items64);
+  if (hipStreamSynchronize(st) != hipSuccess) rc = FGNN_EHIP;
+  return rc;
 }
 
 extern "C" int fgnn_debug_sort_pairs(uint32_t *d_keys, uint32_t *d_vals, size_t n, void *stream) {

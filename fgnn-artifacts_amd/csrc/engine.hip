@@ -1036,3 +1036,50 @@ extern "C" const uint32_t *fgnn_batch_cache_index_ptr(const fgnn_batch *b, int w
   return (b && which >= 0 && which < 4) ? b->cidx[which] : nullptr;
 }
 extern "C" const fgnn_batch_meta *fgnn_batch_device_meta(const fgnn_batch *b) { return b ? b->d_meta : nullptr; }
+
+// ---- fgnn_debug_scan_*: the descriptor sets (fgnn::ScanWsHost) a handle owns, for the tests of their wrap-arounds ----
+namespace {
+int debug_scan_hosts(int kind, void *handle, fgnn::ScanWsHost **out) {  // out: room for 2 * kSlots
+  if (!handle) return FGNN_EINVAL;
+  int n = 0;
+  if (kind == FGNN_DEBUG_SCAN_OF_SAMPLER) {
+    for (auto &sl : static_cast<fgnn_sampler *>(handle)->slot) {
+      out[n++] = &sl.scan_sample;  // (also the weighted samplers' seed-ranking prefix: fgnn::RankWs points here)
+      out[n++] = sl.ht ? sl.ht->scan : nullptr;
+    }
+  } else if (kind == FGNN_DEBUG_SCAN_OF_HASHTABLE) {
+    out[n++] = static_cast<fgnn_hashtable *>(handle)->scan;
+  } else if (kind == FGNN_DEBUG_SCAN_OF_BATCH) {
+    out[n++] = static_cast<fgnn_batch *>(handle)->scan;
+  } else {
+    return FGNN_EINVAL;
+  }
+  for (int i = 0; i < n; ++i)
+    if (!out[i]) return FGNN_EINVAL;
+  return n;
+}
+}  // namespace
+
+extern "C" int fgnn_debug_scan_count(int handle_kind, const void *handle) {
+  fgnn::ScanWsHost *hosts[2 * kSlots];
+  return debug_scan_hosts(handle_kind, const_cast<void *>(handle), hosts);
+}
+
+extern "C" int fgnn_debug_scan_set(int handle_kind, void *handle, long long gen, long long ticket) {
+  fgnn::ScanWsHost *hosts[2 * kSlots];
+  const int n = debug_scan_hosts(handle_kind, handle, hosts);
+  if (n < 0) return n;
+  for (int i = 0; i < n; ++i) {
+    const int rc = hosts[i]->debug_set(gen, ticket);
+    if (rc != FGNN_OK) return rc;
+  }
+  return FGNN_OK;
+}
+
+extern "C" int fgnn_debug_scan_get(int handle_kind, const void *handle, int index, fgnn_debug_scan_state *h_out) {
+  fgnn::ScanWsHost *hosts[2 * kSlots];
+  const int n = debug_scan_hosts(handle_kind, const_cast<void *>(handle), hosts);
+  if (n < 0) return n;
+  if (index < 0 || index >= n) return FGNN_EINVAL;
+  return hosts[index]->debug_get(h_out);
+}

@@ -398,6 +398,7 @@ __device__ __forceinline__ void phase_mark(const ScanWs &w, uint32_t tile, int p
 unsigned long long *phase_log_base();  // capi.hip
 unsigned long long *scan_help_counter();  // capi.hip: device word counting helped tiles (allocated on first use)
 int scan_help_after_override();           // capi.hip: -1 unless fgnn_debug_set_scan_help_after() was called
+bool take_stateless_ticket_start(uint32_t *start);  // capi.hip: fgnn_debug_set_stateless_ticket_start_once, consumed
 // Where a timed-out cross-workgroup wait is reported for launches made by this host thread: the batch driver points
 // it at the batch summary's `overflow` word (so the host sees it with the batch), otherwise the descriptors' own word.
 uint32_t *&scan_error_sink();           // capi.hip (thread-local)
@@ -559,8 +560,10 @@ __device__ __forceinline__ size_t resolve_count64(size_t n_host, const size_t *d
 }
 
 // Exclusive scan of `n` block sums by ONE workgroup of 1024 threads, in place (defined in
-// scan.hip).  total -> *total64 and *total32 (either may be null).  If accum != null the kernel also
-// does *accum_out = *accum + total (used to advance the hash table's item count on the device).
+// scan.hip).  total -> *total64 and *total32 (either may be null).  The arithmetic is 32-bit throughout: prefixes and
+// total are exact modulo 2^32, and *total64 is that 32-bit total zero-extended (every caller bounds its item count
+// below 2^31).  If accum_out != null the kernel also does *accum_out = (accum ? *accum : 0) + total (used to advance the
+// hash table's item count on the device; accum_out may be accum).
 // d_items32 / d_items64 (optional): device count of the items the sums were computed from, items_per_sum
 // of them per entry -- lets the scan skip the capacity padding.
 int launch_scan_block_sums(uint32_t *sums, size_t n, size_t *total64, uint32_t *total32,
@@ -598,8 +601,12 @@ inline int device_cu_count() {
 // host side of ScanWs: owns the descriptors and hands out generations
 struct ScanWsHost {
   ScanWs ws{nullptr, nullptr, 0, 0, nullptr, nullptr, 0, kScanHelpAfterPolls, nullptr};
+  uint32_t wipes = 0;  // times next() wiped the descriptors (diagnostics)
   int create(size_t max_tiles);
   void destroy();
+  // fgnn_debug_scan_set / _get (scan.hip): both synchronise the device
+  int debug_set(long long gen, long long ticket);
+  int debug_get(fgnn_debug_scan_state *out) const;
   // descriptor view for the next launch of `grid` workgroups (all of which call scan_take_tile)
   // kind: which kernel family the launch belongs to (0 sampler, 1 dedup count+assign, 2 cache split) -- selects
   // the section of the diagnostic phase log
@@ -615,6 +622,7 @@ struct ScanWsHost {
       (void)hipMemset(ws.desc, 0, (size_t)ws.max_tiles * sizeof(unsigned long long));
       (void)hipDeviceSynchronize();
       ws.gen = 0;
+      ++wipes;
     }
     ws.gen += 1u;
     ScanWs v = ws;

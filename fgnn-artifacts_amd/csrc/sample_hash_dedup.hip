@@ -131,6 +131,11 @@ int sample_hash_dedup(const uint32_t *indptr, const uint32_t *indices, const flo
     scan.max_tiles = (uint32_t)nb;
     scan.ticket = reinterpret_cast<uint32_t *>(scan.desc + nb);
     scan.ticket_base = 0;
+    uint32_t t0;
+    if (take_stateless_ticket_start(&t0)) {  // tests: tickets of this launch start next to the counter's wrap
+      FGNN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(scan.ticket), (int)t0, 1, st));
+      scan.ticket_base = t0;
+    }
   }
 #define FGNN_HD(MODE)                                                                                              \
   hipLaunchKernelGGL(hash_dedup_kernel, dim3(nb), dim3(kBlock), lds, st, indptr, indices, prob_table, alias_table, \

@@ -57,6 +57,37 @@ void ScanWsHost::destroy() {
   ws.ticket = nullptr;
 }
 
+int ScanWsHost::debug_set(long long gen, long long ticket) {
+  if (!ws.desc || gen > 0x3FFFFFFELL) return FGNN_EINVAL;
+  FGNN_HIP_CHECK(hipDeviceSynchronize());  // nothing in flight draws tickets or polls descriptors meanwhile
+  if (ticket >= 0) {
+    const uint32_t t = (uint32_t)ticket;
+    FGNN_HIP_CHECK(hipMemcpy(ws.ticket, &t, sizeof(t), hipMemcpyHostToDevice));
+    ws.ticket_base = t;
+  }
+  if (gen >= 0) ws.gen = (uint32_t)gen;
+  return FGNN_OK;
+}
+
+int ScanWsHost::debug_get(fgnn_debug_scan_state *out) const {
+  if (!ws.desc || !out) return FGNN_EINVAL;
+  FGNN_HIP_CHECK(hipDeviceSynchronize());
+  unsigned long long *h = static_cast<unsigned long long *>(malloc((size_t)ws.max_tiles * sizeof(unsigned long long)));
+  if (!h) return FGNN_ENOSPC;
+  uint32_t word = 0, top = 0;
+  const bool ok = hipMemcpy(h, ws.desc, (size_t)ws.max_tiles * sizeof(unsigned long long), hipMemcpyDeviceToHost) ==
+                      hipSuccess &&
+                  hipMemcpy(&word, ws.ticket, sizeof(word), hipMemcpyDeviceToHost) == hipSuccess;
+  for (uint32_t i = 0; ok && i < ws.max_tiles; ++i) {
+    const uint32_t g = (uint32_t)(h[i] >> 32) >> 2;
+    if (g > top) top = g;
+  }
+  free(h);
+  if (!ok) return FGNN_EHIP;
+  *out = fgnn_debug_scan_state{ws.gen, ws.ticket_base, word, wipes, top, ws.max_tiles};
+  return FGNN_OK;
+}
+
 int launch_scan_block_sums(uint32_t *sums, size_t n, size_t *total64, uint32_t *total32, const uint32_t *accum,
                            uint32_t *accum_out, hipStream_t stream, const uint32_t *d_items32, uint32_t items_per_sum,
                            const size_t *d_items64) {

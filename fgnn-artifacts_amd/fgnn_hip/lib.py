@@ -34,7 +34,7 @@ _T2DT = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.uint8
          torch.int8: I8, torch.int64: I64}
 
 EXPORTS = [
-    "fgnn_version", "fgnn_last_error", "fgnn_device_count", "fgnn_debug_phase_log_bytes", "fgnn_debug_phase_log", "fgnn_debug_occupy", "fgnn_debug_scan_helps", "fgnn_debug_set_scan_help_after", "fgnn_debug_set_partition_lds_limit", "fgnn_debug_sort_pairs", "fgnn_debug_random_reads", "fgnn_scratch_bytes", "fgnn_sanity_map_bytes", "fgnn_sanity_check_batch", "fgnn_sample_khop0", "fgnn_sample_khop2",
+    "fgnn_version", "fgnn_last_error", "fgnn_device_count", "fgnn_debug_phase_log_bytes", "fgnn_debug_phase_log", "fgnn_debug_occupy", "fgnn_debug_scan_helps", "fgnn_debug_set_scan_help_after", "fgnn_debug_set_partition_lds_limit", "fgnn_debug_sort_pairs", "fgnn_debug_scan_block_sums", "fgnn_debug_scan_count", "fgnn_debug_scan_set", "fgnn_debug_scan_get", "fgnn_debug_set_stateless_ticket_start_once", "fgnn_debug_random_reads", "fgnn_scratch_bytes", "fgnn_sanity_map_bytes", "fgnn_sanity_check_batch", "fgnn_sample_khop0", "fgnn_sample_khop2",
     "fgnn_weighted_scratch_bytes", "fgnn_sample_weighted_khop_prefix", "fgnn_random_walk_scratch_bytes",
     "fgnn_sample_random_walk", "fgnn_sample_khop1", "fgnn_sample_weighted_khop",
     "fgnn_hash_dedup_scratch_bytes", "fgnn_sample_weighted_khop_hash_dedup",
@@ -78,6 +78,23 @@ _TRAIN_SIGNATURES = {
 }
 
 
+class DebugScanState(C.Structure):
+    """fgnn_debug_scan_state (fgnn_hip.h)"""
+    _fields_ = [("gen", C.c_uint32), ("ticket_base", C.c_uint32), ("ticket_word", C.c_uint32), ("wipes", C.c_uint32),
+                ("max_desc_gen", C.c_uint32), ("max_tiles", C.c_uint32)]
+
+
+SCAN_OF_SAMPLER, SCAN_OF_HASHTABLE, SCAN_OF_BATCH = 0, 1, 2  # FGNN_DEBUG_SCAN_OF_*
+SCAN_GEN_LIMIT = 0x3FFFFFFE  # the last generation of a cycle: the launch after it wipes the descriptors and carries 1
+_DEBUG_SCAN_SIGNATURES = {
+    "fgnn_debug_scan_block_sums": (_I, [_P, _Z, _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
+    "fgnn_debug_scan_count": (_I, [_I, _P]),
+    "fgnn_debug_scan_set": (_I, [_I, _P, C.c_longlong, C.c_longlong]),
+    "fgnn_debug_scan_get": (_I, [_I, _P, _I, C.POINTER(DebugScanState)]),
+    "fgnn_debug_set_stateless_ticket_start_once": (None, [C.c_uint32]),
+}
+
+
 class FgnnError(RuntimeError):
     pass
 
@@ -111,6 +128,9 @@ def load():
         L.fgnn_hashtable_d_num_items.argtypes = [C.c_void_p]
         L.fgnn_debug_set_scan_help_after.restype = None
         L.fgnn_debug_set_scan_help_after.argtypes = [C.c_int]
+        for name, (restype, argtypes) in _DEBUG_SCAN_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         for name, (restype, argtypes) in _TRAIN_SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -192,6 +212,49 @@ def debug_sort_pairs(keys, vals):
     assert keys.numel() == vals.numel()
     _check(load().fgnn_debug_sort_pairs(_ptr(keys), _ptr(vals), C.c_size_t(keys.numel()), _stream()),
            "fgnn_debug_sort_pairs")
+
+
+def _scan_handle(obj):
+    kind = (SCAN_OF_SAMPLER if isinstance(obj, Sampler) else SCAN_OF_HASHTABLE if isinstance(obj, HashTable) else
+            SCAN_OF_BATCH if isinstance(obj, Batch) else None)
+    if kind is None:
+        raise FgnnError("a Sampler, a HashTable or a Batch owns look-back descriptors; %r does not" % (obj,))
+    return kind, obj.h
+
+
+def debug_scan_set(obj, gen=-1, ticket=-1):
+    """fgnn_debug_scan_set: host generation and / or ticket counter (device word and host base) of every look-back
+    descriptor set that `obj` (Sampler, HashTable, Batch) owns; -1 leaves a counter alone.  Synchronises."""
+    kind, h = _scan_handle(obj)
+    _check(load().fgnn_debug_scan_set(kind, h, gen, ticket), "fgnn_debug_scan_set")
+
+
+def debug_scan_states(obj):
+    """fgnn_debug_scan_get for every descriptor set of `obj`: a list of DebugScanState.  Synchronises."""
+    kind, h = _scan_handle(obj)
+    L = load()
+    n = L.fgnn_debug_scan_count(kind, h)
+    if n < 0:
+        _check(n, "fgnn_debug_scan_count")
+    out = []
+    for i in range(n):
+        st = DebugScanState()
+        _check(L.fgnn_debug_scan_get(kind, h, i, C.byref(st)), "fgnn_debug_scan_get")
+        out.append(st)
+    return out
+
+
+def debug_scan_block_sums(sums, n=None, total64=None, total32=None, accum=None, accum_out=None, items32=None,
+                          items64=None, items_per_sum=0):
+    """fgnn_debug_scan_block_sums: the one-workgroup exclusive scan of scan.hip on device tensors (int32 storage for
+    uint32 words, int64[1] for total64 / items64), in place; waits."""
+    _need_gpu(sums, total64, total32, accum, accum_out, items32, items64)
+    n = sums.numel() if n is None else n
+    _check(load().fgnn_debug_scan_block_sums(sums.data_ptr() if n else None, n, *[t.data_ptr() if t is not None else None
+                                                                                  for t in (total64, total32, accum,
+                                                                                            accum_out, items32, items64)],
+                                             items_per_sum, torch.cuda.current_stream().cuda_stream),
+           "fgnn_debug_scan_block_sums")
 
 
 def sample_weighted_khop_prefix(indptr, indices, prefix, inp, fanout, seed, batch_key, layer, src_mode=SRC_GLOBAL,

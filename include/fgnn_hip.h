@@ -76,6 +76,41 @@ void fgnn_debug_set_partition_lds_limit(int distinct_keys);
  * (scan.hip; where the reference calls cub::DeviceRadixSort, cuda_sampling_weighted_khop_prefix.cu:200-215), on its
  * own: n uint32 pairs sorted by key in place, equal keys in their input order.  Allocates its scratch and waits. */
 int fgnn_debug_sort_pairs(uint32_t *d_keys, uint32_t *d_vals, size_t n, void *stream);
+/* Diagnostics (tests/test_scan_wrap_gpu.py): the one-workgroup exclusive scan the samplers and the dedup table fall back
+ * to when a grid is too large for the single-pass prefix (scan.hip), on its own: d_sums[0 .. n) scanned in place modulo
+ * 2^32; the total (modulo 2^32, zero-extended in *d_total64) to *d_total64 / *d_total32 and *d_accum_out =
+ * *d_accum + total (each may be NULL).  With d_items32 or d_items64 only the first
+ * ceil(items / items_per_sum) entries are scanned, the others stay as they are.  Waits for the stream. */
+int fgnn_debug_scan_block_sums(uint32_t *d_sums, size_t n, size_t *d_total64, uint32_t *d_total32,
+                               const uint32_t *d_accum, uint32_t *d_accum_out, const uint32_t *d_items32,
+                               const size_t *d_items64, uint32_t items_per_sum, void *stream);
+/* Diagnostics (tests/test_scan_wrap_gpu.py): the look-back descriptor sets of the single-pass kernels carry two
+ * counters that are never reset -- the launch generation (wiped and restarted after 2^30 - 2 launches) and, for the
+ * ticketed hash-dedup sampler, a 32-bit ticket counter.  These calls put them next to their wrap and read them back.
+ * handle_kind: FGNN_DEBUG_SCAN_OF_SAMPLER (an fgnn_sampler: per slot the sampler's set, index 2 * slot, and the slot's
+ * dedup table's, 2 * slot + 1), _OF_HASHTABLE (an fgnn_hashtable: one set), _OF_BATCH (an fgnn_batch: the cache
+ * split's).  All three synchronise the device; call them only while no call on the handle is running.
+ *   _count: number of descriptor sets the handle owns (negative: error).
+ *   _set: gen >= 0: the host generation of every set becomes `gen` (the next launch carries gen + 1; descriptors are
+ *         left alone, so `gen` must not be below a generation already stamped in the current cycle); ticket >= 0: device
+ *         ticket word and host base of every set both become `ticket` (low 32 bits).  Negative: left as it is.
+ *   _get: state of set `index`. */
+enum { FGNN_DEBUG_SCAN_OF_SAMPLER = 0, FGNN_DEBUG_SCAN_OF_HASHTABLE = 1, FGNN_DEBUG_SCAN_OF_BATCH = 2 };
+typedef struct {
+  uint32_t gen;           /* generation of the last launch */
+  uint32_t ticket_base;   /* host mirror of the ticket counter */
+  uint32_t ticket_word;   /* the device ticket counter */
+  uint32_t wipes;         /* times the descriptors were wiped because the generations ran out */
+  uint32_t max_desc_gen;  /* largest generation stamped in any descriptor */
+  uint32_t max_tiles;     /* descriptors in the set */
+} fgnn_debug_scan_state;
+int fgnn_debug_scan_count(int handle_kind, const void *handle);
+int fgnn_debug_scan_set(int handle_kind, void *handle, long long gen, long long ticket);
+int fgnn_debug_scan_get(int handle_kind, const void *handle, int index, fgnn_debug_scan_state *h_out);
+/* Diagnostics (tests): the stateless fgnn_sample_weighted_khop_hash_dedup keeps its ticket counter in the caller's
+ * scratch and starts it at 0 in every call; the NEXT such call of the process starts it (device word and base) at
+ * `start` instead, once. */
+void fgnn_debug_set_stateless_ticket_start_once(uint32_t start);
 
 /* Bytes of scratch that any single call below needs for `n_cap` items. */
 size_t fgnn_scratch_bytes(size_t n_cap);

@@ -37,6 +37,29 @@ def test_binding_lists_every_export():
     assert sorted(lib.EXPORTS) == _declared("fgnn_hip.h")
 
 
+SCAN_DEBUG_ENTRY_POINTS = ["fgnn_debug_scan_block_sums", "fgnn_debug_scan_count", "fgnn_debug_scan_set",
+                           "fgnn_debug_scan_get", "fgnn_debug_set_stateless_ticket_start_once"]
+
+
+def test_scan_debug_entry_points_are_declared_exported_bound_and_documented(hip_lib):
+    """the hooks tests/test_scan_wrap_gpu.py drives the single-pass scan's counters with: in the header, in the library,
+    in the binding's export list with a signature, and named where INTEGRATION.md lists the debug entry points"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "fgnn-artifacts_amd"))
+    from fgnn_hip import lib
+    declared = _declared("fgnn_hip.h")
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in SCAN_DEBUG_ENTRY_POINTS:
+        assert name in declared and hasattr(hip_lib, name) and name in lib.EXPORTS, name
+        assert name in lib._DEBUG_SCAN_SIGNATURES, name
+        assert "`%s`" % name in doc, name
+    # the read-back structure of the binding mirrors the header's, field for field
+    txt = open(os.path.join(ROOT, "include", "fgnn_hip.h")).read()
+    body = re.search(r"typedef struct \{([^}]*)\} fgnn_debug_scan_state;", txt).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    assert re.findall(r"uint32_t (\w+);", body) == [f for f, _ in lib.DebugScanState._fields_]
+
+
 def test_version_and_scratch(hip_lib):
     hip_lib.fgnn_version.restype = ctypes.c_char_p
     assert b"gfx950" in hip_lib.fgnn_version()
