@@ -50,6 +50,9 @@ constexpr int kPartDedupThreads = 512;
 constexpr int kPartRegPairs = 8;                  // pairs a dedup lane keeps in registers: bins up to 4096 items
 constexpr uint32_t kPartLdsSlots = 8192;          // 64 KiB of 8-byte buckets: two workgroups per CU
 constexpr size_t kPartLdsBytes = kPartLdsSlots * sizeof(unsigned long long) + 16;  // + two counters
+constexpr uint32_t kPartLdsLimit = kPartLdsSlots * 3u / 4u;  // default PartView::lds_limit
+constexpr uint32_t kPartHopeless = 4u * kPartLdsSlots;       // a bin of more items skips the LDS pass
+constexpr uint32_t kPartRegItems = (uint32_t)kPartRegPairs * kPartDedupThreads;  // bins kept in registers: 4096
 // items per bin aimed at (the bin count is the next power of two: bins hold 1024 .. 2048 items, ~0.8 of them distinct:
 // LDS load <= 0.2).  2048 rather than 1536: a papers100M batch (~393 K items) then always gets 256 bins; at 1536 the
 // batches straddled the 256 / 512 boundary and the 512-bin ones cost the whole path 1 % (two builds alternating)
@@ -331,7 +334,7 @@ __global__ __launch_bounds__(kPartDedupThreads) void part_dedup_kernel(PartView 
     const uint32_t beg = p.bin_base[b], cnt = p.bin_base[b + 1] - beg;
     // bins of up to kPartRegPairs x 512 items (all of them unless a hub node piles its duplicates into one): a lane's
     // pairs stay in registers between the insert and the read-back
-    const bool in_regs = cnt <= (uint32_t)kPartRegPairs * kPartDedupThreads;
+    const bool in_regs = cnt <= kPartRegItems;
     uint2 kv[kPartRegPairs];
     if (in_regs) {
 #pragma unroll
@@ -349,7 +352,7 @@ __global__ __launch_bounds__(kPartDedupThreads) void part_dedup_kernel(PartView 
     uint32_t newkeys = 0;
     // more items than four tables' worth: a bin that full (fills beyond 2048 bins x 2048 items, or a run of ids that
     // collide in the hash's top bits) almost surely overflows -- straight to the global table, no LDS pass
-    const bool hopeless = cnt > 4u * kPartLdsSlots;
+    const bool hopeless = cnt > kPartHopeless;
     if (hopeless) {
       if (threadIdx.x == 0) sh_overflow = 1u;
     } else if (in_regs) {
@@ -458,7 +461,7 @@ int partition_fill(PartWs *w, const fgnn_hashtable *ht, const uint32_t *items, s
   const HtView tv = ht_view(ht);
   PartView p{w->pairs, w->bins, w->bins + (size_t)kPartMaxBlocks * w->max_bins, w->max_log2,
              g_part_lds_limit.load(std::memory_order_relaxed) >= 0
-                 ? (uint32_t)g_part_lds_limit.load(std::memory_order_relaxed) : kPartLdsSlots * 3u / 4u};
+                 ? (uint32_t)g_part_lds_limit.load(std::memory_order_relaxed) : kPartLdsLimit};
   // tiles are walked with a stride: the count matrix has one row per workgroup
   const size_t tiles = div_up(cap + ht->max_items, (size_t)kPartTile);
   const size_t blocks = tiles < (size_t)kPartMaxBlocks ? tiles : (size_t)kPartMaxBlocks;
@@ -487,4 +490,17 @@ int partition_fill(PartWs *w, const fgnn_hashtable *ht, const uint32_t *items, s
 
 extern "C" void fgnn_debug_set_partition_lds_limit(int distinct_keys) {
   fgnn::g_part_lds_limit.store(distinct_keys, std::memory_order_relaxed);
+}
+
+// read-only: the constants the kernels above were compiled with, in the order fgnn_hip.h documents
+extern "C" void fgnn_debug_partition_params(uint32_t out[8]) {
+  if (!out) return;
+  out[0] = fgnn::kPartMinLog2;
+  out[1] = fgnn::kPartMaxLog2;
+  out[2] = fgnn::kPartPerBin;
+  out[3] = fgnn::kPartLdsSlots;
+  out[4] = fgnn::kPartLdsLimit;
+  out[5] = fgnn::kPartRegItems;
+  out[6] = fgnn::kPartHopeless;
+  out[7] = (uint32_t)fgnn::kPartTile;
 }

@@ -34,7 +34,7 @@ _T2DT = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.uint8
          torch.int8: I8, torch.int64: I64}
 
 EXPORTS = [
-    "fgnn_version", "fgnn_last_error", "fgnn_device_count", "fgnn_debug_phase_log_bytes", "fgnn_debug_phase_log", "fgnn_debug_occupy", "fgnn_debug_scan_helps", "fgnn_debug_set_scan_help_after", "fgnn_debug_set_partition_lds_limit", "fgnn_debug_sort_pairs", "fgnn_debug_scan_block_sums", "fgnn_debug_scan_count", "fgnn_debug_scan_set", "fgnn_debug_scan_get", "fgnn_debug_set_stateless_ticket_start_once", "fgnn_debug_random_reads", "fgnn_scratch_bytes", "fgnn_sanity_map_bytes", "fgnn_sanity_check_batch", "fgnn_sample_khop0", "fgnn_sample_khop2",
+    "fgnn_version", "fgnn_last_error", "fgnn_device_count", "fgnn_debug_phase_log_bytes", "fgnn_debug_phase_log", "fgnn_debug_occupy", "fgnn_debug_scan_helps", "fgnn_debug_set_scan_help_after", "fgnn_debug_set_partition_lds_limit", "fgnn_debug_partition_params", "fgnn_debug_sort_pairs", "fgnn_debug_scan_block_sums", "fgnn_debug_scan_count", "fgnn_debug_scan_set", "fgnn_debug_scan_get", "fgnn_debug_set_stateless_ticket_start_once", "fgnn_debug_random_reads", "fgnn_scratch_bytes", "fgnn_sanity_map_bytes", "fgnn_sanity_check_batch", "fgnn_sample_khop0", "fgnn_sample_khop2",
     "fgnn_weighted_scratch_bytes", "fgnn_sample_weighted_khop_prefix", "fgnn_random_walk_scratch_bytes",
     "fgnn_sample_random_walk", "fgnn_sample_khop1", "fgnn_sample_weighted_khop",
     "fgnn_hash_dedup_scratch_bytes", "fgnn_sample_weighted_khop_hash_dedup",
@@ -95,6 +95,14 @@ _DEBUG_SCAN_SIGNATURES = {
 }
 
 
+# fgnn_debug_partition_params: names of out[0 .. 8), in order
+PARTITION_PARAMS = ("min_log2", "max_log2", "per_bin", "lds_slots", "lds_limit", "reg_items", "hopeless_items", "tile")
+_DEBUG_PARTITION_SIGNATURES = {
+    "fgnn_debug_set_partition_lds_limit": (None, [_I]),
+    "fgnn_debug_partition_params": (None, [C.POINTER(C.c_uint32)]),
+}
+
+
 class FgnnError(RuntimeError):
     pass
 
@@ -129,6 +137,9 @@ def load():
         L.fgnn_debug_set_scan_help_after.restype = None
         L.fgnn_debug_set_scan_help_after.argtypes = [C.c_int]
         for name, (restype, argtypes) in _DEBUG_SCAN_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        for name, (restype, argtypes) in _DEBUG_PARTITION_SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         for name, (restype, argtypes) in _TRAIN_SIGNATURES.items():
@@ -242,6 +253,14 @@ def debug_scan_states(obj):
         _check(L.fgnn_debug_scan_get(kind, h, i, C.byref(st)), "fgnn_debug_scan_get")
         out.append(st)
     return out
+
+
+def debug_partition_params():
+    """fgnn_debug_partition_params: {name: value} of the partitioned fill's compiled-in constants (PARTITION_PARAMS).
+    Needs no GPU."""
+    out = (C.c_uint32 * len(PARTITION_PARAMS))()
+    load().fgnn_debug_partition_params(out)
+    return dict(zip(PARTITION_PARAMS, (int(v) for v in out)))
 
 
 def debug_scan_block_sums(sums, n=None, total64=None, total32=None, accum=None, accum_out=None, items32=None,
@@ -372,6 +391,10 @@ class HashTable:
         _check(load().fgnn_hashtable_map(self.h, _ptr(items), C.c_size_t(items.numel()), C.c_void_p(0),
                                          C.c_size_t(items.numel()), _ptr(mapped), _stream()), "fgnn_hashtable_map")
         return mapped[:items.numel()]
+
+    def capacity(self):
+        """buckets of the table: the power of two >= max(1024, 2 * max_items)"""
+        return int(load().fgnn_hashtable_capacity(self.h))
 
     def num_items(self):
         """Synchronises."""

@@ -72,6 +72,13 @@ void fgnn_debug_set_scan_help_after(int polls);
  * table before the bin falls back to the global table; a small value forces the fall-back path, a negative one
  * restores the default (3/4 of the 8192 slots). */
 void fgnn_debug_set_partition_lds_limit(int distinct_keys);
+/* Diagnostics (tests/test_hashtable_adversarial_gpu.py): the constants the partitioned fill was compiled with, read-only:
+ * out[0], out[1] = smallest and largest log2 of a fill's bin count, out[2] = items per bin aimed at (the bin count is
+ * the power of two that brings a fill of known nodes + items to at most that many per bin, within those bounds),
+ * out[3] = slots of a bin's LDS table, out[4] = the default distinct-key limit (see above), out[5] = largest bin whose
+ * pairs stay in registers, out[6] = largest bin that is tried in LDS at all, out[7] = items per histogram / scatter
+ * tile.  Touches no device. */
+void fgnn_debug_partition_params(uint32_t out[8]);
 /* Diagnostics (tests): the stable (key, value) sort the stateless with-replacement samplers order their seeds with
  * (scan.hip; where the reference calls cub::DeviceRadixSort, cuda_sampling_weighted_khop_prefix.cu:200-215), on its
  * own: n uint32 pairs sorted by key in place, equal keys in their input order.  Allocates its scratch and waits. */

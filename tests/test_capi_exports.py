@@ -60,6 +60,33 @@ def test_scan_debug_entry_points_are_declared_exported_bound_and_documented(hip_
     assert re.findall(r"uint32_t (\w+);", body) == [f for f, _ in lib.DebugScanState._fields_]
 
 
+PARTITION_DEBUG_ENTRY_POINTS = ["fgnn_debug_set_partition_lds_limit", "fgnn_debug_partition_params"]
+
+
+def test_partition_debug_entry_points_are_declared_exported_bound_and_documented(hip_lib):
+    """the hooks tests/test_hashtable_adversarial_gpu.py places its cases with: in the header, in the library, in the
+    binding's export list with a signature, and named where INTEGRATION.md lists the debug entry points; the read-only
+    one answers without a GPU, with the values tests/golden/partition_params.json records"""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "fgnn-artifacts_amd"))
+    from fgnn_hip import lib
+    declared = _declared("fgnn_hip.h")
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in PARTITION_DEBUG_ENTRY_POINTS:
+        assert name in declared and hasattr(hip_lib, name) and name in lib.EXPORTS, name
+        assert name in lib._DEBUG_PARTITION_SIGNATURES, name
+        assert "`%s`" % name in doc, name
+    assert "fgnn_hashtable_capacity" in declared and "fgnn_hashtable_capacity" in lib.EXPORTS
+    assert callable(getattr(lib.HashTable, "capacity", None))
+    out = (ctypes.c_uint32 * 8)(*([0xDEADBEEF] * 8))
+    hip_lib.fgnn_debug_partition_params.restype = None
+    hip_lib.fgnn_debug_partition_params(out)
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "partition_params.json")))
+    assert list(golden) == list(lib.PARTITION_PARAMS)
+    assert [int(v) for v in out] == [golden[k] for k in lib.PARTITION_PARAMS]
+
+
 def test_version_and_scratch(hip_lib):
     hip_lib.fgnn_version.restype = ctypes.c_char_p
     assert b"gfx950" in hip_lib.fgnn_version()
