@@ -33,49 +33,133 @@ F32, F64, F16, U8, I32, I8, I64 = range(7)
 _T2DT = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.uint8: U8, torch.int32: I32,
          torch.int8: I8, torch.int64: I64}
 
-EXPORTS = [
-    "fgnn_version", "fgnn_last_error", "fgnn_device_count", "fgnn_debug_phase_log_bytes", "fgnn_debug_phase_log", "fgnn_debug_occupy", "fgnn_debug_scan_helps", "fgnn_debug_set_scan_help_after", "fgnn_debug_set_partition_lds_limit", "fgnn_debug_partition_params", "fgnn_debug_sort_pairs", "fgnn_debug_scan_block_sums", "fgnn_debug_scan_count", "fgnn_debug_scan_set", "fgnn_debug_scan_get", "fgnn_debug_set_stateless_ticket_start_once", "fgnn_debug_random_reads", "fgnn_scratch_bytes", "fgnn_sanity_map_bytes", "fgnn_sanity_check_batch", "fgnn_sample_khop0", "fgnn_sample_khop2",
-    "fgnn_weighted_scratch_bytes", "fgnn_sample_weighted_khop_prefix", "fgnn_random_walk_scratch_bytes",
-    "fgnn_sample_random_walk", "fgnn_sample_khop1", "fgnn_sample_weighted_khop",
-    "fgnn_hash_dedup_scratch_bytes", "fgnn_sample_weighted_khop_hash_dedup",
-    "fgnn_hashtable_create", "fgnn_hashtable_create_ex", "fgnn_hashtable_destroy", "fgnn_hashtable_capacity", "fgnn_hashtable_reset",
-    "fgnn_hashtable_fill_unique", "fgnn_hashtable_fill_duplicates", "fgnn_hashtable_map", "fgnn_hashtable_n2o",
-    "fgnn_hashtable_d_num_items", "fgnn_hashtable_set_n2o", "fgnn_hashtable_start_batch",
-    "fgnn_extract_neighbour_scratch_bytes", "fgnn_extract_neighbour", "fgnn_neighbourhood_expand",
-    "fgnn_presample_count", "fgnn_presample_rank_scratch_bytes", "fgnn_presample_rank", "fgnn_cache_table_build",
-    "fgnn_cache_table_replace", "fgnn_get_miss_cache_index", "fgnn_gather_rows", "fgnn_gather_rows_masked", "fgnn_gather_rows_shared", "fgnn_extract_fused", "fgnn_extract_fused_grid", "fgnn_extract_fused_link_grid", "fgnn_block_aggregate", "fgnn_block_aggregate_ex", "fgnn_batch_set_feat_row_mask",
-    "fgnn_sage_finish_z", "fgnn_sage_grad_prep", "fgnn_relu_dropout", "fgnn_relu_dropout_backward",
-    "fgnn_softmax_xent_scratch_bytes", "fgnn_softmax_xent", "fgnn_adam_step",
-    "fgnn_block_degrees", "fgnn_block_aggregate_scaled", "fgnn_relu_l2norm", "fgnn_relu_l2norm_backward",
-    "fgnn_gat_workspace_bytes", "fgnn_gat_forward", "fgnn_gat_backward",
-]
-
 _lib = None
 
-# The training-side entry points (fgnn_hip/nn.py) as include/fgnn_hip.h declares them: return type, argument types.
-# Pointers travel as addresses (an int, a c_void_p or None), so the call sites pass data_ptr() values and plain numbers.
-_P, _Z, _I, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_float
-_PP, _PZ = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
-_TRAIN_SIGNATURES = {
-    "fgnn_block_aggregate": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _P]),
-    "fgnn_block_aggregate_ex": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P]),
-    "fgnn_block_aggregate_scaled": (_I, [_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P]),
-    "fgnn_block_degrees": (_I, [_P, _P, _P, _Z, _P, _P, _P]),
-    "fgnn_relu_l2norm": (_I, [_P, _Z, _P, _Z, _P, _Z, _Z, _P]),
-    "fgnn_relu_l2norm_backward": (_I, [_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P]),
-    "fgnn_gat_workspace_bytes": (_Z, [_Z, _Z, _Z]),
-    "fgnn_gat_forward": (_I, [_P, _P, _Z, _P, _P, _P, _Z, _Z, _Z, _Z, _F, _F, C.c_uint64, _P, C.c_uint32, _P, _P, _Z, _P,
-                              _Z, _P]),
-    "fgnn_gat_backward": (_I, [_P, _P, _Z, _P, _P, _P, _Z, _P, _P, _Z, _Z, _Z, _Z, _F, _F, C.c_uint64, _P, C.c_uint32, _P,
-                               _Z, _P, _P, _P, _Z, _P]),
-    "fgnn_sage_finish_z": (_I, [_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P]),
-    "fgnn_sage_grad_prep": (_I, [_P, _Z, _P, _P, _P, _Z, _Z, _Z, _P]),
-    "fgnn_relu_dropout": (_I, [_P, _P, _Z, _F, C.c_uint64, _P, C.c_uint32, _P]),
-    "fgnn_relu_dropout_backward": (_I, [_P, _P, _P, _Z, _F, _P]),
-    "fgnn_softmax_xent_scratch_bytes": (_Z, [_Z]),
-    "fgnn_softmax_xent": (_I, [_P, _Z, _P, _Z, _Z, _P, _P, _Z, _P, _Z, _P]),
-    "fgnn_adam_step": (_I, [_PP, _PP, _PP, _PP, _PZ, _I, _F, _F, _F, _F, _F, _P, _P]),
+# Every function include/fgnn_hip.h declares: return type, argument types, derived from the prototype by rule
+# (tests/test_binding_signatures.py compares the two).  Any pointer, array, handle, structure pointer or stream is a
+# c_void_p -- it takes an int address, None, a c_void_p, byref(x) or a ctypes array -- and a scalar is its ctypes twin,
+# so the call sites pass addresses and plain numbers.  load() applies the table; nothing else types a function.
+_P, _S, _I, _U, _Z, _U32, _U64 = C.c_void_p, C.c_char_p, C.c_int, C.c_uint, C.c_size_t, C.c_uint32, C.c_uint64
+_LL, _ULL, _F, _D = C.c_longlong, C.c_ulonglong, C.c_float, C.c_double
+SIGNATURES = {
+    "fgnn_version": (_S, ()),
+    "fgnn_last_error": (_S, ()),
+    "fgnn_device_count": (_I, ()),
+    "fgnn_debug_phase_log_bytes": (_Z, ()),
+    "fgnn_debug_phase_log": (None, (_P,)),
+    "fgnn_debug_occupy": (_I, (_Z, _U, _P)),
+    "fgnn_debug_random_reads": (_I, (_P, _Z, _Z, _U64, _P, _P)),
+    "fgnn_debug_scan_helps": (_ULL, ()),
+    "fgnn_debug_set_scan_help_after": (None, (_I,)),
+    "fgnn_debug_set_partition_lds_limit": (None, (_I,)),
+    "fgnn_debug_partition_params": (None, (_P,)),
+    "fgnn_debug_sort_pairs": (_I, (_P, _P, _Z, _P)),
+    "fgnn_debug_scan_block_sums": (_I, (_P, _Z, _P, _P, _P, _P, _P, _P, _U32, _P)),
+    "fgnn_debug_scan_count": (_I, (_I, _P)),
+    "fgnn_debug_scan_set": (_I, (_I, _P, _LL, _LL)),
+    "fgnn_debug_scan_get": (_I, (_I, _P, _I, _P)),
+    "fgnn_debug_set_stateless_ticket_start_once": (None, (_U32,)),
+    "fgnn_scratch_bytes": (_Z, (_Z,)),
+    "fgnn_sanity_map_bytes": (_Z, (_Z,)),
+    "fgnn_sanity_check_batch": (_I, (_P, _Z, _P, _Z, _U32, _P, _P)),
+    "fgnn_sample_khop0": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32, _P, _Z, _P)),
+    "fgnn_sample_khop2": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32, _P, _Z, _P)),
+    "fgnn_weighted_scratch_bytes": (_Z, (_Z, _Z)),
+    "fgnn_sample_weighted_khop_prefix": (_I, (_P, _P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32, _P, _Z,
+                                            _P)),
+    "fgnn_sample_khop1": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32, _P, _Z, _P)),
+    "fgnn_sample_weighted_khop": (_I, (_P, _P, _P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32, _P, _Z,
+                                     _P)),
+    "fgnn_hash_dedup_scratch_bytes": (_Z, (_Z,)),
+    "fgnn_sample_weighted_khop_hash_dedup": (_I, (_P, _P, _P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32,
+                                                _P, _Z, _P)),
+    "fgnn_random_walk_scratch_bytes": (_Z, (_Z, _Z)),
+    "fgnn_sample_random_walk": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _D, _Z, _Z, _P, _P, _P, _P, _I, _U64, _U64, _U32, _P,
+                                   _Z, _P)),
+    "fgnn_extract_neighbour_scratch_bytes": (_Z, (_Z,)),
+    "fgnn_extract_neighbour": (_I, (_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _Z, _P)),
+    "fgnn_neighbourhood_expand": (_I, (_P, _P, _P, _Z, _P, _Z, _P, _U32, _P, _P, _Z, _P, _I, _P)),
+    "fgnn_hashtable_create": (_P, (_Z, _P)),
+    "fgnn_hashtable_create_ex": (_P, (_Z, _Z, _P)),
+    "fgnn_hashtable_destroy": (None, (_P,)),
+    "fgnn_hashtable_capacity": (_Z, (_P,)),
+    "fgnn_hashtable_reset": (_I, (_P, _P)),
+    "fgnn_hashtable_fill_unique": (_I, (_P, _P, _Z, _P)),
+    "fgnn_hashtable_fill_duplicates": (_I, (_P, _P, _Z, _P, _Z, _P, _P, _Z, _P)),
+    "fgnn_hashtable_map": (_I, (_P, _P, _Z, _P, _Z, _P, _P)),
+    "fgnn_hashtable_set_n2o": (_I, (_P, _P)),
+    "fgnn_hashtable_start_batch": (_I, (_P, _P, _Z, _P, _P, _U64, _U32, _P)),
+    "fgnn_hashtable_n2o": (_P, (_P,)),
+    "fgnn_hashtable_d_num_items": (_P, (_P,)),
+    "fgnn_get_miss_cache_index": (_I, (_P, _P, _Z, _P, _Z, _P, _P, _P, _P, _P, _P, _Z, _P)),
+    "fgnn_cache_table_replace": (_I, (_P, _P, _Z, _P, _Z, _P)),
+    "fgnn_gather_rows": (_I, (_P, _P, _P, _P, _Z, _P, _Z, _Z, _I, _P)),
+    "fgnn_gather_rows_masked": (_I, (_P, _P, _P, _P, _Z, _P, _Z, _Z, _I, _U32, _P)),
+    "fgnn_gather_rows_shared": (_I, (_P, _P, _P, _P, _Z, _P, _Z, _Z, _I, _U32, _I, _P)),
+    "fgnn_extract_fused": (_I, (_P, _P)),
+    "fgnn_extract_fused_grid": (_Z, (_P,)),
+    "fgnn_extract_fused_link_grid": (_Z, (_P,)),
+    "fgnn_block_aggregate": (_I, (_P, _P, _P, _Z, _P, _Z, _P, _P)),
+    "fgnn_block_aggregate_ex": (_I, (_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P)),
+    "fgnn_block_degrees": (_I, (_P, _P, _P, _Z, _P, _P, _P)),
+    "fgnn_block_aggregate_scaled": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P)),
+    "fgnn_relu_l2norm": (_I, (_P, _Z, _P, _Z, _P, _Z, _Z, _P)),
+    "fgnn_relu_l2norm_backward": (_I, (_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P)),
+    "fgnn_gat_workspace_bytes": (_Z, (_Z, _Z, _Z)),
+    "fgnn_gat_forward": (_I, (_P, _P, _Z, _P, _P, _P, _Z, _Z, _Z, _Z, _F, _F, _U64, _P, _U32, _P, _P, _Z, _P, _Z, _P)),
+    "fgnn_gat_backward": (_I, (_P, _P, _Z, _P, _P, _P, _Z, _P, _P, _Z, _Z, _Z, _Z, _F, _F, _U64, _P, _U32, _P, _Z, _P,
+                             _P, _P, _Z, _P)),
+    "fgnn_sage_finish_z": (_I, (_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P)),
+    "fgnn_sage_grad_prep": (_I, (_P, _Z, _P, _P, _P, _Z, _Z, _Z, _P)),
+    "fgnn_relu_dropout": (_I, (_P, _P, _Z, _F, _U64, _P, _U32, _P)),
+    "fgnn_relu_dropout_backward": (_I, (_P, _P, _P, _Z, _F, _P)),
+    "fgnn_softmax_xent_scratch_bytes": (_Z, (_Z,)),
+    "fgnn_softmax_xent": (_I, (_P, _Z, _P, _Z, _Z, _P, _P, _Z, _P, _Z, _P)),
+    "fgnn_adam_step": (_I, (_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _P, _P)),
+    "fgnn_presample_count": (_I, (_P, _P, _Z, _P, _Z, _P)),
+    "fgnn_presample_rank_scratch_bytes": (_Z, (_Z,)),
+    "fgnn_presample_rank": (_I, (_P, _Z, _P, _P, _Z, _P)),
+    "fgnn_cache_table_build": (_I, (_P, _Z, _P, _Z, _P)),
+    "fgnn_sampler_create": (_P, (_P, _P)),
+    "fgnn_sampler_destroy": (None, (_P,)),
+    "fgnn_sampler_prefix_tree_stats": (_I, (_P, _P)),
+    "fgnn_sampler_max_nodes": (_Z, (_P,)),
+    "fgnn_sampler_max_edges": (_Z, (_P, _I)),
+    "fgnn_batch_create": (_P, (_P, _Z, _I, _I, _Z, _P)),
+    "fgnn_batch_destroy": (None, (_P,)),
+    "fgnn_sampler_sample": (_I, (_P, _P, _Z, _U64, _P, _P)),
+    "fgnn_sampler_sample_indexed": (_I, (_P, _P, _Z, _U64, _P, _P, _P)),
+    "fgnn_sampler_sample_ordered": (_I, (_P, _U64, _P, _Z, _U64, _P, _P)),
+    "fgnn_sampler_sample_begin": (_I, (_P, _P, _Z, _U64, _P, _P, _P)),
+    "fgnn_sampler_sample_begin_ordered": (_I, (_P, _U64, _P, _Z, _U64, _P, _P)),
+    "fgnn_sampler_sample_end": (_I, (_P, _U64, _P, _P, _P)),
+    "fgnn_sampler_run_batch": (_I, (_P, _U64, _P, _Z, _U64, _P, _P, _P, _P, _P)),
+    "fgnn_sampler_run_range": (_I, (_P, _P, _U64, _Z, _P, _P, _P)),
+    "fgnn_batch_cache_index": (_I, (_P, _P, _P)),
+    "fgnn_batch_set_feat_row_mask": (_I, (_P, _U32)),
+    "fgnn_batch_extract": (_I, (_P, _P, _P, _P)),
+    "fgnn_batch_extract_cached": (_I, (_P, _P, _P, _P, _P)),
+    "fgnn_sampler_run_batch_cached": (_I, (_P, _U64, _P, _Z, _U64, _P, _P, _P, _P, _P, _P)),
+    "fgnn_batch_extract_cached_ms": (_I, (_P, _P)),
+    "fgnn_batch_extract_launch_ms": (_F, (_P,)),
+    "fgnn_batch_enable_timing": (_I, (_P, _I)),
+    "fgnn_batch_gather_ms": (_F, (_P,)),
+    "fgnn_batch_gather_kernel_ms": (_F, (_P,)),
+    "fgnn_batch_finish": (_I, (_P, _P)),
+    "fgnn_batch_host_meta": (_P, (_P,)),
+    "fgnn_batch_meta_copied": (_I, (_P,)),
+    "fgnn_batch_wait": (_I, (_P, _P)),
+    "fgnn_batch_row": (_P, (_P, _I)),
+    "fgnn_batch_col": (_P, (_P, _I)),
+    "fgnn_batch_data": (_P, (_P, _I)),
+    "fgnn_batch_input_nodes": (_P, (_P,)),
+    "fgnn_batch_output_nodes": (_P, (_P,)),
+    "fgnn_batch_feat": (_P, (_P,)),
+    "fgnn_batch_label": (_P, (_P,)),
+    "fgnn_batch_cache_index_ptr": (_P, (_P, _I)),
+    "fgnn_batch_device_meta": (_P, (_P,)),
 }
+EXPORTS = list(SIGNATURES)
 
 
 class DebugScanState(C.Structure):
@@ -86,21 +170,9 @@ class DebugScanState(C.Structure):
 
 SCAN_OF_SAMPLER, SCAN_OF_HASHTABLE, SCAN_OF_BATCH = 0, 1, 2  # FGNN_DEBUG_SCAN_OF_*
 SCAN_GEN_LIMIT = 0x3FFFFFFE  # the last generation of a cycle: the launch after it wipes the descriptors and carries 1
-_DEBUG_SCAN_SIGNATURES = {
-    "fgnn_debug_scan_block_sums": (_I, [_P, _Z, _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
-    "fgnn_debug_scan_count": (_I, [_I, _P]),
-    "fgnn_debug_scan_set": (_I, [_I, _P, C.c_longlong, C.c_longlong]),
-    "fgnn_debug_scan_get": (_I, [_I, _P, _I, C.POINTER(DebugScanState)]),
-    "fgnn_debug_set_stateless_ticket_start_once": (None, [C.c_uint32]),
-}
-
 
 # fgnn_debug_partition_params: names of out[0 .. 8), in order
 PARTITION_PARAMS = ("min_log2", "max_log2", "per_bin", "lds_slots", "lds_limit", "reg_items", "hopeless_items", "tile")
-_DEBUG_PARTITION_SIGNATURES = {
-    "fgnn_debug_set_partition_lds_limit": (None, [_I]),
-    "fgnn_debug_partition_params": (None, [C.POINTER(C.c_uint32)]),
-}
 
 
 class FgnnError(RuntimeError):
@@ -115,34 +187,7 @@ def load():
             raise FgnnError(f"{LIB_PATH} is missing: build it with `make -C fgnn-artifacts_amd/csrc` "
                             "(there is no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        L.fgnn_version.restype = C.c_char_p
-        L.fgnn_last_error.restype = C.c_char_p
-        L.fgnn_debug_scan_helps.restype = C.c_ulonglong
-        L.fgnn_debug_phase_log_bytes.restype = C.c_size_t
-        L.fgnn_debug_phase_log.restype = None
-        L.fgnn_debug_phase_log.argtypes = [C.c_void_p]
-        L.fgnn_scratch_bytes.restype = C.c_size_t
-        L.fgnn_scratch_bytes.argtypes = [C.c_size_t]
-        L.fgnn_extract_neighbour_scratch_bytes.restype = C.c_size_t
-        L.fgnn_extract_neighbour_scratch_bytes.argtypes = [C.c_size_t]
-        L.fgnn_hashtable_create.restype = C.c_void_p
-        L.fgnn_hashtable_create.argtypes = [C.c_size_t, C.POINTER(C.c_int)]
-        L.fgnn_hashtable_destroy.argtypes = [C.c_void_p]
-        L.fgnn_hashtable_capacity.restype = C.c_size_t
-        L.fgnn_hashtable_capacity.argtypes = [C.c_void_p]
-        L.fgnn_hashtable_n2o.restype = C.c_void_p
-        L.fgnn_hashtable_n2o.argtypes = [C.c_void_p]
-        L.fgnn_hashtable_d_num_items.restype = C.c_void_p
-        L.fgnn_hashtable_d_num_items.argtypes = [C.c_void_p]
-        L.fgnn_debug_set_scan_help_after.restype = None
-        L.fgnn_debug_set_scan_help_after.argtypes = [C.c_int]
-        for name, (restype, argtypes) in _DEBUG_SCAN_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        for name, (restype, argtypes) in _DEBUG_PARTITION_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        for name, (restype, argtypes) in _TRAIN_SIGNATURES.items():
+        for name, (restype, argtypes) in SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         # (neither the library nor this binding reads a switch from the environment: tests that force the helping path of
@@ -171,11 +216,13 @@ class DevicePointer:
 
 
 def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else 0)
+    """device-visible address of a tensor or a DevicePointer; None (a null pointer) for None"""
+    return t.data_ptr() if t is not None else None
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _stream(t=None):
+    """handle of the current stream of the current device, or, given a tensor, of that tensor's device"""
+    return torch.cuda.current_stream(t.device if t is not None else None).cuda_stream
 
 
 def _need_gpu(*tensors):
@@ -210,9 +257,8 @@ def sample_khop(kind, indptr, indices, inp, fanout, seed, batch_key, layer, src_
         if kind == "khop0":  # room for the hub tables: rows beyond 16 K entries are then drawn by the whole chip
             ws = torch.empty(ws.numel() + 4 * (n + 16 + 1024 * (fanout + 3)), dtype=torch.uint8, device=dev)
     fn = L.fgnn_sample_khop0 if kind == "khop0" else L.fgnn_sample_khop2
-    code = fn(_ptr(indptr), _ptr(indices), _ptr(inp), C.c_size_t(n), _ptr(d_num_input), C.c_size_t(n),
-              C.c_size_t(fanout), _ptr(out_src), _ptr(out_dst), _ptr(d_num_out), C.c_int(src_mode), C.c_uint64(seed),
-              C.c_uint64(batch_key), C.c_uint32(layer), _ptr(ws), C.c_size_t(ws.numel()), _stream())
+    code = fn(_ptr(indptr), _ptr(indices), _ptr(inp), n, _ptr(d_num_input), n, fanout, _ptr(out_src), _ptr(out_dst),
+              _ptr(d_num_out), src_mode, seed, batch_key, layer, _ptr(ws), ws.numel(), _stream())
     _check(code, "fgnn_sample_" + kind)
     return out_src, out_dst, d_num_out
 
@@ -221,8 +267,7 @@ def debug_sort_pairs(keys, vals):
     """fgnn_debug_sort_pairs: (keys, vals) int32 CUDA tensors sorted in place by key (as uint32), stable."""
     _need_gpu(keys, vals)
     assert keys.numel() == vals.numel()
-    _check(load().fgnn_debug_sort_pairs(_ptr(keys), _ptr(vals), C.c_size_t(keys.numel()), _stream()),
-           "fgnn_debug_sort_pairs")
+    _check(load().fgnn_debug_sort_pairs(_ptr(keys), _ptr(vals), keys.numel(), _stream()), "fgnn_debug_sort_pairs")
 
 
 def _scan_handle(obj):
@@ -269,10 +314,8 @@ def debug_scan_block_sums(sums, n=None, total64=None, total32=None, accum=None, 
     uint32 words, int64[1] for total64 / items64), in place; waits."""
     _need_gpu(sums, total64, total32, accum, accum_out, items32, items64)
     n = sums.numel() if n is None else n
-    _check(load().fgnn_debug_scan_block_sums(sums.data_ptr() if n else None, n, *[t.data_ptr() if t is not None else None
-                                                                                  for t in (total64, total32, accum,
-                                                                                            accum_out, items32, items64)],
-                                             items_per_sum, torch.cuda.current_stream().cuda_stream),
+    _check(load().fgnn_debug_scan_block_sums(_ptr(sums) if n else None, n, _ptr(total64), _ptr(total32), _ptr(accum),
+                                             _ptr(accum_out), _ptr(items32), _ptr(items64), items_per_sum, _stream()),
            "fgnn_debug_scan_block_sums")
 
 
@@ -280,18 +323,15 @@ def sample_weighted_khop_prefix(indptr, indices, prefix, inp, fanout, seed, batc
                                 d_num_input=None):
     L = load()
     _need_gpu(indptr, indices, prefix, inp)
-    L.fgnn_weighted_scratch_bytes.restype = C.c_size_t
     n, dev = inp.numel(), inp.device
     out_src = torch.empty(max(n * fanout, 1), dtype=torch.int32, device=dev)
     out_dst = torch.empty(max(n * fanout, 1), dtype=torch.int32, device=dev)
     d_num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(L.fgnn_weighted_scratch_bytes(C.c_size_t(max(n, 1)), C.c_size_t(fanout)), dtype=torch.uint8,
-                     device=dev)
-    _check(L.fgnn_sample_weighted_khop_prefix(_ptr(indptr), _ptr(indices), _ptr(prefix), _ptr(inp), C.c_size_t(n),
-                                              _ptr(d_num_input), C.c_size_t(n), C.c_size_t(fanout), _ptr(out_src),
-                                              _ptr(out_dst), _ptr(d_num_out), C.c_int(src_mode), C.c_uint64(seed),
-                                              C.c_uint64(batch_key), C.c_uint32(layer), _ptr(ws),
-                                              C.c_size_t(ws.numel()), _stream()), "fgnn_sample_weighted_khop_prefix")
+    ws = torch.empty(L.fgnn_weighted_scratch_bytes(max(n, 1), fanout), dtype=torch.uint8, device=dev)
+    _check(L.fgnn_sample_weighted_khop_prefix(_ptr(indptr), _ptr(indices), _ptr(prefix), _ptr(inp), n,
+                                              _ptr(d_num_input), n, fanout, _ptr(out_src), _ptr(out_dst),
+                                              _ptr(d_num_out), src_mode, seed, batch_key, layer, _ptr(ws), ws.numel(),
+                                              _stream()), "fgnn_sample_weighted_khop_prefix")
     return out_src, out_dst, d_num_out
 
 
@@ -300,16 +340,13 @@ def sample_with_replacement(kind, indptr, indices, inp, fanout, seed, batch_key,
     """kind in {'khop1', 'weighted_khop' (alias method), 'weighted_khop_hash_dedup'}."""
     L = load()
     _need_gpu(indptr, indices, inp)
-    L.fgnn_weighted_scratch_bytes.restype = C.c_size_t
     n, dev = inp.numel(), inp.device
     out_src = torch.empty(max(n * fanout, 1), dtype=torch.int32, device=dev)
     out_dst = torch.empty(max(n * fanout, 1), dtype=torch.int32, device=dev)
     d_num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(L.fgnn_weighted_scratch_bytes(C.c_size_t(max(n, 1)), C.c_size_t(fanout)), dtype=torch.uint8,
-                     device=dev)
-    tail = (_ptr(inp), C.c_size_t(n), C.c_void_p(0), C.c_size_t(n), C.c_size_t(fanout), _ptr(out_src), _ptr(out_dst),
-            _ptr(d_num_out), C.c_int(src_mode), C.c_uint64(seed), C.c_uint64(batch_key), C.c_uint32(layer), _ptr(ws),
-            C.c_size_t(ws.numel()), _stream())
+    ws = torch.empty(L.fgnn_weighted_scratch_bytes(max(n, 1), fanout), dtype=torch.uint8, device=dev)
+    tail = (_ptr(inp), n, None, n, fanout, _ptr(out_src), _ptr(out_dst), _ptr(d_num_out), src_mode, seed, batch_key,
+            layer, _ptr(ws), ws.numel(), _stream())
     if kind == "khop1":
         _check(L.fgnn_sample_khop1(_ptr(indptr), _ptr(indices), *tail), "fgnn_sample_khop1")
     elif kind == "weighted_khop_hash_dedup":
@@ -325,17 +362,13 @@ def sample_random_walk(indptr, indices, inp, walk_len, restart_prob, num_walks, 
                        src_mode=SRC_GLOBAL, d_num_input=None):
     L = load()
     _need_gpu(indptr, indices, inp)
-    L.fgnn_random_walk_scratch_bytes.restype = C.c_size_t
     n, dev = inp.numel(), inp.device
     outs = [torch.empty(max(n * K, 1), dtype=torch.int32, device=dev) for _ in range(3)]
     d_num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(L.fgnn_random_walk_scratch_bytes(C.c_size_t(max(n, 1)), C.c_size_t(K)), dtype=torch.uint8,
-                     device=dev)
-    _check(L.fgnn_sample_random_walk(_ptr(indptr), _ptr(indices), _ptr(inp), C.c_size_t(n), _ptr(d_num_input),
-                                     C.c_size_t(n), C.c_size_t(walk_len), C.c_double(restart_prob),
-                                     C.c_size_t(num_walks), C.c_size_t(K), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
-                                     _ptr(d_num_out), C.c_int(src_mode), C.c_uint64(seed), C.c_uint64(batch_key),
-                                     C.c_uint32(layer), _ptr(ws), C.c_size_t(ws.numel()), _stream()),
+    ws = torch.empty(L.fgnn_random_walk_scratch_bytes(max(n, 1), K), dtype=torch.uint8, device=dev)
+    _check(L.fgnn_sample_random_walk(_ptr(indptr), _ptr(indices), _ptr(inp), n, _ptr(d_num_input), n, walk_len,
+                                     restart_prob, num_walks, K, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                     _ptr(d_num_out), src_mode, seed, batch_key, layer, _ptr(ws), ws.numel(), _stream()),
            "fgnn_sample_random_walk")
     return outs[0], outs[1], outs[2], d_num_out
 
@@ -348,12 +381,10 @@ class HashTable:
         L = load()
         torch.cuda.set_device(device)
         err = C.c_int(0)
-        L.fgnn_hashtable_create_ex.restype = C.c_void_p
         if max_fill_items is None:
-            self.h = C.c_void_p(L.fgnn_hashtable_create(C.c_size_t(max_items), C.byref(err)))
+            self.h = L.fgnn_hashtable_create(max_items, C.byref(err))
         else:
-            self.h = C.c_void_p(L.fgnn_hashtable_create_ex(C.c_size_t(max_items), C.c_size_t(max_fill_items),
-                                                           C.byref(err)))
+            self.h = L.fgnn_hashtable_create_ex(max_items, max_fill_items, C.byref(err))
         if not self.h:
             raise FgnnError(f"fgnn_hashtable_create failed with code {err.value}")
         self.max_items = max_items
@@ -369,7 +400,7 @@ class HashTable:
 
     def fill_unique(self, items):
         _need_gpu(items)
-        _check(load().fgnn_hashtable_fill_unique(self.h, _ptr(items), C.c_size_t(items.numel()), _stream()),
+        _check(load().fgnn_hashtable_fill_unique(self.h, _ptr(items), items.numel(), _stream()),
                "fgnn_hashtable_fill_unique")
 
     def fill_duplicates(self, items, num_items=None, d_num_items=None, want_mapped=True, ws=None):
@@ -380,16 +411,15 @@ class HashTable:
         mapped = torch.empty(max(cap, 1), dtype=torch.int32, device=items.device) if want_mapped else None
         if ws is None:
             ws = scratch(cap, items.device)
-        _check(load().fgnn_hashtable_fill_duplicates(self.h, _ptr(items), C.c_size_t(n), _ptr(d_num_items),
-                                                     C.c_size_t(cap), _ptr(mapped), _ptr(ws), C.c_size_t(ws.numel()),
-                                                     _stream()), "fgnn_hashtable_fill_duplicates")
+        _check(load().fgnn_hashtable_fill_duplicates(self.h, _ptr(items), n, _ptr(d_num_items), cap, _ptr(mapped),
+                                                     _ptr(ws), ws.numel(), _stream()), "fgnn_hashtable_fill_duplicates")
         return mapped
 
     def map(self, items):
         _need_gpu(items)
         mapped = torch.empty(max(items.numel(), 1), dtype=torch.int32, device=items.device)
-        _check(load().fgnn_hashtable_map(self.h, _ptr(items), C.c_size_t(items.numel()), C.c_void_p(0),
-                                         C.c_size_t(items.numel()), _ptr(mapped), _stream()), "fgnn_hashtable_map")
+        _check(load().fgnn_hashtable_map(self.h, _ptr(items), items.numel(), None, items.numel(), _ptr(mapped),
+                                         _stream()), "fgnn_hashtable_map")
         return mapped[:items.numel()]
 
     def capacity(self):
@@ -434,9 +464,8 @@ def extract_neighbour(indptr, indices, inp, out_cap, num_input=None, d_num_input
     out = torch.empty(max(out_cap, 1), dtype=torch.int32, device=dev)
     d_num_out = torch.full((1,), -1, dtype=torch.int64, device=dev)
     ws = torch.empty(L.fgnn_extract_neighbour_scratch_bytes(cap), dtype=torch.uint8, device=dev)
-    _check(L.fgnn_extract_neighbour(_ptr(indptr), _ptr(indices), _ptr(inp), C.c_size_t(n), _ptr(d_num_input),
-                                    C.c_size_t(cap), _ptr(out), C.c_size_t(out_cap), _ptr(d_num_out), _ptr(ws),
-                                    C.c_size_t(ws.numel()), _stream()), "fgnn_extract_neighbour")
+    _check(L.fgnn_extract_neighbour(_ptr(indptr), _ptr(indices), _ptr(inp), n, _ptr(d_num_input), cap, _ptr(out),
+                                    out_cap, _ptr(d_num_out), _ptr(ws), ws.numel(), _stream()), "fgnn_extract_neighbour")
     return out, d_num_out
 
 
@@ -446,10 +475,9 @@ def neighbourhood_expand(indptr, indices, frontier, stamp, mark, freq, nxt, d_nu
     _need_gpu(indptr, indices, frontier, stamp, nxt, d_num_next)
     cap = frontier.numel()
     n = cap if num_frontier is None else num_frontier
-    _check(load().fgnn_neighbourhood_expand(_ptr(indptr), _ptr(indices), _ptr(frontier), C.c_size_t(n),
-                                            _ptr(d_num_frontier), C.c_size_t(cap), _ptr(stamp), C.c_uint32(mark),
-                                            _ptr(freq), _ptr(nxt), C.c_size_t(nxt.numel()), _ptr(d_num_next),
-                                            C.c_int(1 if mark_frontier else 0), _stream()), "fgnn_neighbourhood_expand")
+    _check(load().fgnn_neighbourhood_expand(_ptr(indptr), _ptr(indices), _ptr(frontier), n, _ptr(d_num_frontier), cap,
+                                            _ptr(stamp), mark, _ptr(freq), _ptr(nxt), nxt.numel(), _ptr(d_num_next),
+                                            1 if mark_frontier else 0, _stream()), "fgnn_neighbourhood_expand")
 
 
 class SanityChecker:
@@ -458,10 +486,8 @@ class SanityChecker:
     the batch), 4 = an id >= num_node.  new_epoch() clears the seen-bitmap."""
 
     def __init__(self, num_node, device, invalid_val=EMPTY):
-        L = load()
-        L.fgnn_sanity_map_bytes.restype = C.c_size_t
         self.num_node, self.invalid = num_node, invalid_val
-        self.bits = torch.zeros(L.fgnn_sanity_map_bytes(C.c_size_t(num_node)) // 4, dtype=torch.int32, device=device)
+        self.bits = torch.zeros(load().fgnn_sanity_map_bytes(num_node) // 4, dtype=torch.int32, device=device)
         self.flags = torch.zeros(1, dtype=torch.int32, device=device)
 
     def new_epoch(self):
@@ -470,9 +496,9 @@ class SanityChecker:
     def check(self, batch, no_duplicates=True):
         _need_gpu(batch)
         self.flags.zero_()
-        _check(load().fgnn_sanity_check_batch(_ptr(self.bits) if no_duplicates else None, C.c_size_t(self.num_node),
-                                              _ptr(batch), C.c_size_t(batch.numel()), C.c_uint32(self.invalid),
-                                              _ptr(self.flags), _stream()), "fgnn_sanity_check_batch")
+        _check(load().fgnn_sanity_check_batch(_ptr(self.bits) if no_duplicates else None, self.num_node, _ptr(batch),
+                                              batch.numel(), self.invalid, _ptr(self.flags), _stream()),
+               "fgnn_sanity_check_batch")
         return int(self.flags.item())
 
 
@@ -481,20 +507,18 @@ def presample_count(freq, nodes, num_nodes=None, d_num_nodes=None):
     _need_gpu(freq, nodes)
     cap = nodes.numel()
     n = cap if num_nodes is None else num_nodes
-    _check(load().fgnn_presample_count(_ptr(freq), _ptr(nodes), C.c_size_t(n), _ptr(d_num_nodes), C.c_size_t(cap),
-                                       _stream()), "fgnn_presample_count")
+    _check(load().fgnn_presample_count(_ptr(freq), _ptr(nodes), n, _ptr(d_num_nodes), cap, _stream()),
+           "fgnn_presample_count")
 
 
 def presample_rank(freq):
     """rank list (int32 device tensor, u32 storage): nodes by (frequency desc, id desc) (dist/pre_sampler.cc:140-160)."""
     L = load()
     _need_gpu(freq)
-    L.fgnn_presample_rank_scratch_bytes.restype = C.c_size_t
     n = freq.numel()
-    ws = torch.empty(L.fgnn_presample_rank_scratch_bytes(C.c_size_t(n)), dtype=torch.uint8, device=freq.device)
+    ws = torch.empty(L.fgnn_presample_rank_scratch_bytes(n), dtype=torch.uint8, device=freq.device)
     rank = torch.empty(n, dtype=torch.int32, device=freq.device)
-    _check(L.fgnn_presample_rank(_ptr(freq), C.c_size_t(n), _ptr(rank), _ptr(ws), C.c_size_t(ws.numel()), _stream()),
-           "fgnn_presample_rank")
+    _check(L.fgnn_presample_rank(_ptr(freq), n, _ptr(rank), _ptr(ws), ws.numel(), _stream()), "fgnn_presample_rank")
     return rank
 
 
@@ -503,8 +527,7 @@ def cache_table_build(rank, num_cached, num_node=None):
     _need_gpu(rank)
     n = rank.numel() if num_node is None else num_node
     table = torch.empty(n, dtype=torch.int32, device=rank.device)
-    _check(load().fgnn_cache_table_build(_ptr(table), C.c_size_t(n), _ptr(rank), C.c_size_t(num_cached), _stream()),
-           "fgnn_cache_table_build")
+    _check(load().fgnn_cache_table_build(_ptr(table), n, _ptr(rank), num_cached, _stream()), "fgnn_cache_table_build")
     return table
 
 
@@ -512,9 +535,8 @@ def cache_table_replace(table, old_nodes, new_nodes):
     """ReplaceCacheGPU's index update: old nodes -> EMPTY, new node i -> i"""
     _need_gpu(table, old_nodes, new_nodes)
     n_old = 0 if old_nodes is None else old_nodes.numel()
-    _check(load().fgnn_cache_table_replace(_ptr(table), _ptr(old_nodes) if n_old else C.c_void_p(0), C.c_size_t(n_old),
-                                           _ptr(new_nodes), C.c_size_t(new_nodes.numel()), _stream()),
-           "fgnn_cache_table_replace")
+    _check(load().fgnn_cache_table_replace(_ptr(table), _ptr(old_nodes) if n_old else None, n_old, _ptr(new_nodes),
+                                           new_nodes.numel(), _stream()), "fgnn_cache_table_replace")
 
 
 def get_miss_cache_index(table, nodes, num_nodes=None, d_num_nodes=None, ws=None):
@@ -527,10 +549,9 @@ def get_miss_cache_index(table, nodes, num_nodes=None, d_num_nodes=None, ws=None
     d_counts = torch.zeros(2, dtype=torch.int32, device=dev)
     if ws is None:
         ws = scratch(cap, dev)
-    _check(load().fgnn_get_miss_cache_index(_ptr(table), _ptr(nodes), C.c_size_t(n), _ptr(d_num_nodes),
-                                            C.c_size_t(cap), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
-                                            _ptr(outs[3]), _ptr(d_counts), _ptr(ws), C.c_size_t(ws.numel()),
-                                            _stream()), "fgnn_get_miss_cache_index")
+    _check(load().fgnn_get_miss_cache_index(_ptr(table), _ptr(nodes), n, _ptr(d_num_nodes), cap, _ptr(outs[0]),
+                                            _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(d_counts), _ptr(ws),
+                                            ws.numel(), _stream()), "fgnn_get_miss_cache_index")
     return outs[0], outs[1], outs[2], outs[3], d_counts
 
 
@@ -546,19 +567,16 @@ def gather_rows(out, src, src_index=None, dst_index=None, n=None, d_n=None, src_
     assert out.dtype == src.dtype and out.is_contiguous() and src.is_contiguous()
     if shared_gpu is not None:
         mask = 0xFFFFFFFF if src_row_mask is None else src_row_mask
-        _check(load().fgnn_gather_rows_shared(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), C.c_size_t(n),
-                                              _ptr(d_n), C.c_size_t(n), C.c_size_t(dim), C.c_int(_T2DT[out.dtype]),
-                                              C.c_uint32(mask), C.c_int(int(shared_gpu)), _stream()),
+        _check(load().fgnn_gather_rows_shared(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), n, _ptr(d_n), n,
+                                              dim, _T2DT[out.dtype], mask, int(shared_gpu), _stream()),
                "fgnn_gather_rows_shared")
         return out
     if src_row_mask is not None:
-        _check(load().fgnn_gather_rows_masked(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), C.c_size_t(n),
-                                              _ptr(d_n), C.c_size_t(n), C.c_size_t(dim), C.c_int(_T2DT[out.dtype]),
-                                              C.c_uint32(src_row_mask), _stream()), "fgnn_gather_rows_masked")
+        _check(load().fgnn_gather_rows_masked(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), n, _ptr(d_n), n,
+                                              dim, _T2DT[out.dtype], src_row_mask, _stream()), "fgnn_gather_rows_masked")
         return out
-    _check(load().fgnn_gather_rows(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), C.c_size_t(n), _ptr(d_n),
-                                   C.c_size_t(n), C.c_size_t(dim), C.c_int(_T2DT[out.dtype]), _stream()),
-           "fgnn_gather_rows")
+    _check(load().fgnn_gather_rows(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), n, _ptr(d_n), n, dim,
+                                   _T2DT[out.dtype], _stream()), "fgnn_gather_rows")
     return out
 
 
@@ -570,8 +588,8 @@ def random_read_rate(array, num_items=4_000_000, repeats=24):
     L = load()
 
     def launch(salt):
-        _check(L.fgnn_debug_random_reads(_ptr(array), C.c_size_t(array.numel()), C.c_size_t(num_items), C.c_uint64(salt),
-                                         _ptr(sink), _stream()), "fgnn_debug_random_reads")
+        _check(L.fgnn_debug_random_reads(_ptr(array), array.numel(), num_items, salt, _ptr(sink), _stream()),
+               "fgnn_debug_random_reads")
     launch(1)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -598,12 +616,6 @@ class ExtractJob(C.Structure):
                 ("stamps", C.c_void_p)]
 
 
-def _raw(t):
-    """device-visible address of a tensor, a DevicePointer or None (C.c_void_p field value)"""
-    p = _ptr(t)
-    return p.value if isinstance(p, C.c_void_p) else p
-
-
 def extract_fused(out, miss_rows, cache_rows, miss_src, miss_dst, cache_src, cache_dst, num_miss=None, num_cache=None,
                   d_counts=None, miss_row_mask=0xFFFFFFFF, label_out=None, label_src=None, label_index=None,
                   copies=(), link_workgroups=0, stamps=None):
@@ -615,26 +627,24 @@ def extract_fused(out, miss_rows, cache_rows, miss_src, miss_dst, cache_src, cac
     for s in out.shape[1:]:
         dim *= s
     j = ExtractJob()
-    j.out, j.miss_rows, j.cache_rows = _raw(out), _raw(miss_rows), _raw(cache_rows)
-    j.miss_src, j.miss_dst, j.cache_src, j.cache_dst = _raw(miss_src), _raw(miss_dst), _raw(cache_src), _raw(cache_dst)
+    j.out, j.miss_rows, j.cache_rows = _ptr(out), _ptr(miss_rows), _ptr(cache_rows)
+    j.miss_src, j.miss_dst, j.cache_src, j.cache_dst = _ptr(miss_src), _ptr(miss_dst), _ptr(cache_src), _ptr(cache_dst)
     j.num_miss = (miss_src.numel() if miss_src is not None else 0) if num_miss is None else num_miss
     j.num_cache = (cache_src.numel() if cache_src is not None else 0) if num_cache is None else num_cache
     if d_counts is not None:
-        j.d_counts = _raw(d_counts)
+        j.d_counts = _ptr(d_counts)
         j.cap = max(miss_src.numel() if miss_src is not None else 0, cache_src.numel() if cache_src is not None else 0)
     j.dim, j.dtype, j.miss_row_mask = dim, _T2DT[out.dtype], miss_row_mask
     if label_out is not None:
-        j.label_out, j.label_src, j.label_index = _raw(label_out), _raw(label_src), _raw(label_index)
+        j.label_out, j.label_src, j.label_index = _ptr(label_out), _ptr(label_src), _ptr(label_index)
         j.num_label, j.label_dtype = label_index.numel(), _T2DT[label_out.dtype]
     segs = (CopySegment * max(len(copies), 1))()
     for k, (d, s, words) in enumerate(copies):
-        segs[k].dst, segs[k].src, segs[k].words = _raw(d), _raw(s), words
+        segs[k].dst, segs[k].src, segs[k].words = _ptr(d), _ptr(s), words
     j.segs, j.num_segs = segs, len(copies)
     j.link_workgroups = link_workgroups
-    j.stamps = _raw(stamps)
+    j.stamps = _ptr(stamps)
     L = load()
-    L.fgnn_extract_fused_grid.restype = C.c_size_t
-    L.fgnn_extract_fused_link_grid.restype = C.c_size_t
     _check(L.fgnn_extract_fused(C.byref(j), _stream()), "fgnn_extract_fused")
     return int(L.fgnn_extract_fused_grid(C.byref(j))), int(L.fgnn_extract_fused_link_grid(C.byref(j)))
 
@@ -644,16 +654,6 @@ def extract_fused(out, miss_rows, cache_rows, miss_src, miss_dst, cache_src, cac
 
 MAX_LAYERS = 8
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP = 0, 1, 2, 3, 4, 5, 6
-
-EXPORTS += [
-    "fgnn_sampler_create", "fgnn_sampler_destroy", "fgnn_sampler_max_nodes", "fgnn_sampler_max_edges",
-    "fgnn_batch_create", "fgnn_batch_destroy", "fgnn_sampler_sample", "fgnn_sampler_sample_ordered",
-    "fgnn_sampler_run_batch", "fgnn_batch_enable_timing", "fgnn_batch_gather_ms", "fgnn_batch_cache_index", "fgnn_batch_extract",
-    "fgnn_batch_extract_cached", "fgnn_sampler_run_batch_cached", "fgnn_batch_extract_cached_ms", "fgnn_batch_extract_launch_ms", "fgnn_batch_gather_kernel_ms", "fgnn_batch_finish", "fgnn_batch_wait", "fgnn_batch_row", "fgnn_batch_col",
-    "fgnn_batch_data", "fgnn_batch_input_nodes", "fgnn_batch_output_nodes", "fgnn_batch_feat", "fgnn_batch_label",
-    "fgnn_batch_cache_index_ptr", "fgnn_batch_device_meta", "fgnn_batch_host_meta", "fgnn_batch_meta_copied",
-    "fgnn_sampler_run_range", "fgnn_sampler_sample_indexed", "fgnn_sampler_sample_begin", "fgnn_sampler_sample_begin_ordered", "fgnn_sampler_sample_end", "fgnn_sampler_prefix_tree_stats",
-]
 
 
 class SamplerConfig(C.Structure):
@@ -703,20 +703,11 @@ class Sampler:
                  walk_len=0, num_walks=0, restart_prob=0.0, prob_table=None, alias_table=None):
         L = load()
         _need_gpu(indptr, indices)
-        L.fgnn_sampler_create.restype = C.c_void_p
-        L.fgnn_sampler_max_nodes.restype = C.c_size_t
-        L.fgnn_sampler_max_edges.restype = C.c_size_t
-        L.fgnn_batch_create.restype = C.c_void_p
-        for name in ("fgnn_batch_row", "fgnn_batch_col", "fgnn_batch_data", "fgnn_batch_input_nodes",
-                     "fgnn_batch_output_nodes", "fgnn_batch_feat", "fgnn_batch_label", "fgnn_batch_cache_index_ptr",
-                     "fgnn_batch_device_meta"):
-            getattr(L, name).restype = C.c_void_p
         self.device = indptr.device
         torch.cuda.set_device(self.device)
         self._keep = (indptr, indices, prob_prefix, prob_table, alias_table)
         cfg = SamplerConfig()
-        cfg.indptr, cfg.indices = indptr.data_ptr(), indices.data_ptr()
-        cfg.prob_prefix = prob_prefix.data_ptr() if prob_prefix is not None else 0
+        cfg.indptr, cfg.indices, cfg.prob_prefix = _ptr(indptr), _ptr(indices), _ptr(prob_prefix)
         cfg.num_node = indptr.numel() - 1
         cfg.sample_type = sample_type
         cfg.num_layers = len(fanout)
@@ -724,12 +715,11 @@ class Sampler:
             cfg.fanout[i] = f
         cfg.max_batch_size, cfg.seed = max_batch_size, seed
         cfg.walk_len, cfg.num_walks, cfg.restart_prob = walk_len, num_walks, restart_prob
-        cfg.prob_table = prob_table.data_ptr() if prob_table is not None else 0
-        cfg.alias_table = alias_table.data_ptr() if alias_table is not None else 0
+        cfg.prob_table, cfg.alias_table = _ptr(prob_table), _ptr(alias_table)
         if prob_prefix is not None:
             torch.cuda.synchronize(self.device)  # the sampler reads the table while it is created (search trees)
         err = C.c_int(0)
-        self.h = C.c_void_p(L.fgnn_sampler_create(C.byref(cfg), C.byref(err)))
+        self.h = L.fgnn_sampler_create(C.byref(cfg), C.byref(err))
         if not self.h:
             raise FgnnError(f"fgnn_sampler_create failed with code {err.value} {L.fgnn_last_error().decode()}")
         self.fanout = list(fanout)
@@ -748,7 +738,7 @@ class Sampler:
         return int(out[0]), int(out[1]), int(out[2])
 
     def max_edges(self, layer):
-        return load().fgnn_sampler_max_edges(self.h, C.c_int(layer))
+        return load().fgnn_sampler_max_edges(self.h, layer)
 
     def new_batch(self, feat_dim=0, feat_dtype=F32, label_dtype=I64, feat_rows_cap=0):
         return Batch(self, feat_dim, feat_dtype, label_dtype, feat_rows_cap)
@@ -757,44 +747,39 @@ class Sampler:
         """seq=None: internal call counter (single-threaded use); else the explicit batch order (thread-safe)."""
         _need_gpu(seeds)
         if seq is None:
-            _check(load().fgnn_sampler_sample(self.h, _ptr(seeds), C.c_size_t(seeds.numel()), C.c_uint64(batch_key),
-                                              batch.h, _stream()), "fgnn_sampler_sample")
+            _check(load().fgnn_sampler_sample(self.h, _ptr(seeds), seeds.numel(), batch_key, batch.h, _stream()),
+                   "fgnn_sampler_sample")
         else:
-            _check(load().fgnn_sampler_sample_ordered(self.h, C.c_uint64(seq), _ptr(seeds), C.c_size_t(seeds.numel()),
-                                                      C.c_uint64(batch_key), batch.h, _stream()),
-                   "fgnn_sampler_sample_ordered")
+            _check(load().fgnn_sampler_sample_ordered(self.h, seq, _ptr(seeds), seeds.numel(), batch_key, batch.h,
+                                                      _stream()), "fgnn_sampler_sample_ordered")
 
     def sample_indexed(self, seeds, batch_key, batch, cache_table=None):
         """fgnn_sampler_sample_indexed: sample + cache index in one call (an arch5 sampler's batch), internal counter"""
         _need_gpu(seeds)
-        _check(load().fgnn_sampler_sample_indexed(self.h, _ptr(seeds), C.c_size_t(seeds.numel()), C.c_uint64(batch_key),
-                                                  batch.h, _ptr(cache_table), _stream()), "fgnn_sampler_sample_indexed")
+        _check(load().fgnn_sampler_sample_indexed(self.h, _ptr(seeds), seeds.numel(), batch_key, batch.h,
+                                                  _ptr(cache_table), _stream()), "fgnn_sampler_sample_indexed")
 
     def sample_begin(self, seq, seeds, batch_key, batch, stream=None):
         """fgnn_sampler_sample_begin_ordered: the batch's sampling CHAIN (everything up to its last sampler launch).
         Enqueue begin(k + 1) before end(k) to keep khop2's cross-batch chain busy; `stream` of end = that of begin."""
         _need_gpu(seeds)
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        _check(load().fgnn_sampler_sample_begin_ordered(self.h, C.c_uint64(seq), _ptr(seeds), C.c_size_t(seeds.numel()),
-                                                        C.c_uint64(batch_key), batch.h, st),
+        st = (stream or torch.cuda.current_stream()).cuda_stream
+        _check(load().fgnn_sampler_sample_begin_ordered(self.h, seq, _ptr(seeds), seeds.numel(), batch_key, batch.h, st),
                "fgnn_sampler_sample_begin_ordered")
 
     def sample_end(self, seq, batch, cache_table=None, stream=None):
         """fgnn_sampler_sample_end: the batch's TAIL (last dedup fill, fix-ups, table reset) [+ the cache-index split];
         extraction / finish are the caller's, on the same stream"""
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        _check(load().fgnn_sampler_sample_end(self.h, C.c_uint64(seq), batch.h, _ptr(cache_table), st),
-               "fgnn_sampler_sample_end")
+        st = (stream or torch.cuda.current_stream()).cuda_stream
+        _check(load().fgnn_sampler_sample_end(self.h, seq, batch.h, _ptr(cache_table), st), "fgnn_sampler_sample_end")
 
     def run_batch(self, seq, seeds, batch_key, batch, cache_table=None, feat=None, label=None, stream=None):
         """sample + cache index + extract + finish in ONE C call on `stream` (a torch stream; default current).
         Safe to call from several Python threads (ctypes releases the GIL)."""
         _need_gpu(seeds)
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        _check(load().fgnn_sampler_run_batch(self.h, C.c_uint64(seq), _ptr(seeds), C.c_size_t(seeds.numel()),
-                                             C.c_uint64(batch_key), batch.h, _ptr(cache_table), _ptr(feat),
-                                             _ptr(label), st), "fgnn_sampler_run_batch")
-
+        st = (stream or torch.cuda.current_stream()).cuda_stream
+        _check(load().fgnn_sampler_run_batch(self.h, seq, _ptr(seeds), seeds.numel(), batch_key, batch.h,
+                                             _ptr(cache_table), _ptr(feat), _ptr(label), st), "fgnn_sampler_run_batch")
 
     def run_range(self, first_seq, count, train, batch_size, batches, streams, cache_table=None, feat=None, label=None,
                   cache_rows=None, full_feat=None, cached=False):
@@ -819,11 +804,10 @@ class Sampler:
         """sample + cache index + CombineMissData (rows read from `full_feat`: device or pinned host tensor) +
         CombineCacheData + finish in one C call."""
         _need_gpu(seeds, cache_table, cache_rows)
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        _check(load().fgnn_sampler_run_batch_cached(self.h, C.c_uint64(seq), _ptr(seeds), C.c_size_t(seeds.numel()),
-                                                    C.c_uint64(batch_key), batch.h, _ptr(cache_table),
-                                                    _ptr(cache_rows), _ptr(full_feat), _ptr(label), st),
-               "fgnn_sampler_run_batch_cached")
+        st = (stream or torch.cuda.current_stream()).cuda_stream
+        _check(load().fgnn_sampler_run_batch_cached(self.h, seq, _ptr(seeds), seeds.numel(), batch_key, batch.h,
+                                                    _ptr(cache_table), _ptr(cache_rows), _ptr(full_feat), _ptr(label),
+                                                    st), "fgnn_sampler_run_batch_cached")
 
 
 class _RangeCall:
@@ -838,18 +822,14 @@ class _RangeCall:
                       (C.c_void_p * len(streams))(*[st.cuda_stream for st in streams]))
         plan.batches, plan.num_batches = C.cast(self._keep[-2], C.c_void_p), len(batches)
         plan.streams, plan.num_streams = C.cast(self._keep[-1], C.c_void_p), len(streams)
-        plan.cache_table = cache_table.data_ptr() if cache_table is not None else None
-        plan.feat = feat.data_ptr() if feat is not None else None
-        plan.label = label.data_ptr() if label is not None else None
+        plan.cache_table, plan.feat, plan.label = _ptr(cache_table), _ptr(feat), _ptr(label)
         plan.cached = 1 if cached else 0
-        plan.cache_rows = cache_rows.data_ptr() if cache_rows is not None else None
-        plan.full_feat = full_feat.data_ptr() if full_feat is not None else None
+        plan.cache_rows, plan.full_feat = _ptr(cache_rows), _ptr(full_feat)
         self.metas = (BatchMeta * max(count, 1))()
         self.times = (C.c_float * (2 * max(count, 1)))()
         self.busy = C.c_double(0.0)
         self.rc = None
-        self._args = (sampler.h, C.byref(plan), C.c_uint64(first_seq), C.c_size_t(count), self.metas, self.times,
-                      C.byref(self.busy))
+        self._args = (sampler.h, C.byref(plan), first_seq, count, self.metas, self.times, C.byref(self.busy))
 
     def run(self):
         self.rc = self.L.fgnn_sampler_run_range(*self._args)
@@ -871,8 +851,7 @@ class Batch:
         L = load()
         err = C.c_int(0)
         self.sampler = sampler
-        self.h = C.c_void_p(L.fgnn_batch_create(sampler.h, C.c_size_t(feat_dim), C.c_int(feat_dtype),
-                                                C.c_int(label_dtype), C.c_size_t(feat_rows_cap), C.byref(err)))
+        self.h = L.fgnn_batch_create(sampler.h, feat_dim, feat_dtype, label_dtype, feat_rows_cap, C.byref(err))
         if not self.h:
             raise FgnnError(f"fgnn_batch_create failed with code {err.value} {L.fgnn_last_error().decode()}")
         self.feat_dim, self.feat_dtype, self.label_dtype = feat_dim, feat_dtype, label_dtype
@@ -899,10 +878,9 @@ class Batch:
         _check(load().fgnn_batch_finish(self.h, _stream()), "fgnn_batch_finish")
 
     def enable_timing(self, on=True):
-        _check(load().fgnn_batch_enable_timing(self.h, C.c_int(1 if on else 0)), "fgnn_batch_enable_timing")
+        _check(load().fgnn_batch_enable_timing(self.h, 1 if on else 0), "fgnn_batch_enable_timing")
 
     def gather_ms(self):
-        load().fgnn_batch_gather_ms.restype = C.c_float
         return float(load().fgnn_batch_gather_ms(self.h))
 
     def extract_cached_ms(self):
@@ -913,7 +891,6 @@ class Batch:
 
     def extract_launch_ms(self):
         """HIP-event time around the whole one-launch cached extraction (-1 when not timed)"""
-        load().fgnn_batch_extract_launch_ms.restype = C.c_float
         return float(load().fgnn_batch_extract_launch_ms(self.h))
 
     def d_num_input(self):

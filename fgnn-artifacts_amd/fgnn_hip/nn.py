@@ -8,14 +8,9 @@ import torch
 from . import lib as _lib
 
 
-# Argument and return types of every entry point used here are declared once, in lib._TRAIN_SIGNATURES (applied by
-# lib.load()): the calls below pass addresses (lib._ptr: None = null) and plain numbers.
-_ptr = _lib._ptr
-
-
-def _st(t):
-    """the current stream of t's device"""
-    return torch.cuda.current_stream(t.device).cuda_stream
+# Argument and return types of every entry point are declared once, in lib.SIGNATURES (applied by lib.load()): the calls
+# below pass addresses (lib._ptr: None = null), plain numbers and the current stream of a tensor's device (lib._stream).
+_ptr, _st = _lib._ptr, _lib._stream
 
 
 def _aggregate(out, h, src_idx, dst_idx, weight, in_degree=None, scaling=None):

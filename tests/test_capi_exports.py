@@ -51,7 +51,7 @@ def test_scan_debug_entry_points_are_declared_exported_bound_and_documented(hip_
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name in SCAN_DEBUG_ENTRY_POINTS:
         assert name in declared and hasattr(hip_lib, name) and name in lib.EXPORTS, name
-        assert name in lib._DEBUG_SCAN_SIGNATURES, name
+        assert name in lib.SIGNATURES, name
         assert "`%s`" % name in doc, name
     # the read-back structure of the binding mirrors the header's, field for field
     txt = open(os.path.join(ROOT, "include", "fgnn_hip.h")).read()
@@ -75,7 +75,7 @@ def test_partition_debug_entry_points_are_declared_exported_bound_and_documented
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name in PARTITION_DEBUG_ENTRY_POINTS:
         assert name in declared and hasattr(hip_lib, name) and name in lib.EXPORTS, name
-        assert name in lib._DEBUG_PARTITION_SIGNATURES, name
+        assert name in lib.SIGNATURES, name
         assert "`%s`" % name in doc, name
     assert "fgnn_hashtable_capacity" in declared and "fgnn_hashtable_capacity" in lib.EXPORTS
     assert callable(getattr(lib.HashTable, "capacity", None))

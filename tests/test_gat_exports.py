@@ -23,7 +23,7 @@ def test_library_header_and_binding_carry_the_three_entry_points():
     for name, ret in NEW.items():
         assert hasattr(so, name), name
         assert re.search(r"\b%s\s+%s\s*\(" % (ret, name), header), name
-        assert name in lib.EXPORTS and name in lib._TRAIN_SIGNATURES, name
+        assert name in lib.EXPORTS and name in lib.SIGNATURES, name
     decl = re.search(r"int\s+fgnn_gat_forward\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
     for arg in ("src_index", "dst_index", "num_edge", "el", "er", "feat", "num_dst", "negative_slope", "attn_p", "seed",
                 "const unsigned long long *d_step", "tag", "alpha", "out", "out_ld", "ws", "ws_bytes", "stream"):

@@ -224,7 +224,6 @@ def _stateless_hash_dedup(hip, w, d, inp, fanout, batch_key, layer):
     """fgnn_sample_weighted_khop_hash_dedup with a scratch buffer of the test's own, to read the ticket word back: the
     stateless path keeps (workgroups) descriptors and then the counter in it, 8 bytes each"""
     L = hip.load()
-    L.fgnn_hash_dedup_scratch_bytes.restype = C.c_size_t
     n = len(inp)
     nb = (n + 255) // 256
     d_inp = dev(inp)

@@ -237,7 +237,6 @@ def test_softmax_xent_against_float64_reference(hip, c):
     gradient error / bound 0.44; at n = 2500 the kernel's largest gradient deviation is 0.5 - 1.2 x torch's (DESIGN.md
     4.5)."""
     L = hip.load()
-    L.fgnn_softmax_xent_scratch_bytes.restype = C.c_size_t
     ws = torch.zeros((L.fgnn_softmax_xent_scratch_bytes(C.c_size_t(2500)) + 3) // 4, dtype=torch.int32, device="cuda")
     for n in (5, 2500, 5, 1):
         ref_loss, ref_grad, b_loss, b_grad, d_loss, d_grad = R.xent_expectation(c, n)
