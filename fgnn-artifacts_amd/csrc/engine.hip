@@ -18,6 +18,15 @@ constexpr int kSlots = 6;  // batches that may be in flight at once (each on its
                            // multiple of 1, 2, 3 and 6 streams, so that a caller rotating over that many streams
                            // brings every slot back on the stream that used it last (no event between its uses)
 
+// What the chain half of a batch (everything up to its last sampler launch) leaves for its tail half (sample_chain /
+// sample_tail below)
+struct ChainState {
+  bool ran = false;                       // the batch had seeds: layer 0's fill is owed
+  size_t ecap0 = 0;                       // worst-case edges of layer 0 for THIS batch
+  bool resolved0 = false, inserted0 = false;
+  fgnn::FixTail owed = fgnn::no_fix_tail();  // the remap fix-up the layer-1 fill left for the next launch to carry
+};
+
 struct fgnn_sampler {
   fgnn_sampler_config cfg;
   size_t max_nodes;                       // PredictNumNodes(batch, fanout, L)
@@ -45,10 +54,7 @@ struct fgnn_sampler {
       uint64_t seq = 0;
       fgnn_batch *out = nullptr;
       hipStream_t st = nullptr;           // the chain's stream: the tail goes there too
-      bool ran = false;                   // the batch had seeds: layer 0's fill is owed
-      size_t ecap0 = 0;                   // worst-case edges of layer 0 for THIS batch
-      bool resolved0 = false, inserted0 = false;
-      fgnn::FixTail owed;                 // the remap fix-up the layer-1 fill left for the next launch to carry
+      ChainState chain;
     } pend;
     fgnn::ScanWsHost scan_sample;         // look-back descriptors of the single-pass sampler
     uint32_t *rank_bitmap = nullptr;      // with-replacement samplers: seed ranking bitmap over the node ids (all zero
@@ -124,6 +130,11 @@ size_t dtype_size(int dtype) {
   }
 }
 
+// the with-replacement samplers: the driver orders their seeds with a bitmap over the node ids (fgnn::RankWs)
+bool uses_rank_bitmap(int sample_type) {
+  return sample_type == FGNN_WEIGHTED_KHOP_PREFIX || sample_type == FGNN_KHOP1 || sample_type == FGNN_WEIGHTED_KHOP;
+}
+
 }  // namespace
 }  // namespace fgnn
 
@@ -181,9 +192,7 @@ extern "C" fgnn_sampler *fgnn_sampler_create(const fgnn_sampler_config *cfg, int
                 (s->max_edge_cap / 16 + 64) * sizeof(uint32_t);
   for (size_t l = 0; l < cfg->num_layers; ++l) {
     size_t need = 0;
-    if (cfg->sample_type == FGNN_WEIGHTED_KHOP_PREFIX || cfg->sample_type == FGNN_KHOP1 ||
-        cfg->sample_type == FGNN_WEIGHTED_KHOP)
-      need = fgnn_weighted_scratch_bytes(s->in_cap[l], cfg->fanout[l]);
+    if (uses_rank_bitmap(cfg->sample_type)) need = fgnn_weighted_scratch_bytes(s->in_cap[l], cfg->fanout[l]);
     if (cfg->sample_type == FGNN_RANDOM_WALK) need = fgnn_random_walk_scratch_bytes(s->in_cap[l], cfg->fanout[l]);
     if (need > s->ws_bytes) s->ws_bytes = need;
   }
@@ -196,8 +205,7 @@ extern "C" fgnn_sampler *fgnn_sampler_create(const fgnn_sampler_config *cfg, int
     for (hipEvent_t *e : {&sl.done, &sl.csr})
       ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     ok = ok && sl.scan_sample.create(s->max_nodes / 64 + 2) == FGNN_OK;
-    if (cfg->num_node && (cfg->sample_type == FGNN_WEIGHTED_KHOP_PREFIX || cfg->sample_type == FGNN_KHOP1 ||
-                          cfg->sample_type == FGNN_WEIGHTED_KHOP)) {
+    if (cfg->num_node && uses_rank_bitmap(cfg->sample_type)) {
       const size_t bytes = fgnn::rank_ws_bytes(cfg->num_node);
       ok = ok && hipMalloc(&sl.rank_bitmap, bytes) == hipSuccess && hipMemset(sl.rank_bitmap, 0, bytes) == hipSuccess;
     }
@@ -317,21 +325,24 @@ extern "C" fgnn_batch *fgnn_batch_create(const fgnn_sampler *s, size_t feat_dim,
 
 namespace {
 
-// marks the hand-over points of call `seq` even on an early error return, so later calls never wait forever
-struct SeqGuard {
-  fgnn_sampler *s;
-  uint64_t seq;
-  hipStream_t st;
-  bool csr_marked = false;
-  bool finished = false;  // the success path has reset the slot's table and closed the slot itself
-  bool detached = false;  // the batch's chain is enqueued, its tail follows in a later call (Slot::pend): nothing to close yet
-  // end of the slot's use by this batch: remember the stream, record `done` if slots have been seen to change streams
-  void close_slot() {
-    fgnn_sampler::Slot &sl = s->slot[seq % kSlots];
-    sl.done_recorded = sl.expect_cross && hipEventRecord(sl.done, st) == hipSuccess;
-    sl.last_st = st;
-    sl.was_used = true;
-  }
+uint64_t take_seq(fgnn_sampler *s) {  // the unordered entry points' own batch order
+  std::lock_guard<std::mutex> lk(s->mu);
+  return s->next_seq++;
+}
+
+// Marks the hand-over points of call `seq` even on an early error return, so later calls never wait forever.  What a
+// call owes follows from how its guard was made: for_chain -- the CSR hand-over (pass_csr), the slot (close_slot) and
+// the return; for_tail -- the chain half has passed the CSR on: the slot and the return.  detach(): the chain is
+// enqueued and its tail follows in a later call (Slot::pend) -- the CSR turn is taken, this call owes nothing more.
+// Whatever is still open at release() -- the destructor at the latest -- is done there; a slot that was not closed is
+// abandoned first.
+class SeqGuard {
+ public:
+  static SeqGuard for_chain(fgnn_sampler *s, uint64_t seq, hipStream_t st) { return SeqGuard(s, seq, st, false); }
+  static SeqGuard for_tail(fgnn_sampler *s, uint64_t seq, hipStream_t st) { return SeqGuard(s, seq, st, true); }
+  SeqGuard(const SeqGuard &) = delete;
+  ~SeqGuard() { release(); }
+
   // the batch's last sampler kernel has been enqueued on `st` (khop2): record the hand-over event if batches have been
   // seen to follow each other on different streams, then let the next call go on
   void pass_csr(bool record_allowed) {
@@ -342,6 +353,30 @@ struct SeqGuard {
     sl.last_st = st;  // read by the next call (under the mutex released in mark_csr)
     mark_csr();
   }
+  // end of the slot's use by this batch: remember the stream, record `done` if slots have been seen to change streams
+  void close_slot() {
+    fgnn_sampler::Slot &sl = s->slot[seq % kSlots];
+    sl.done_recorded = sl.expect_cross && hipEventRecord(sl.done, st) == hipSuccess;
+    sl.last_st = st;
+    sl.was_used = true;
+    closed = true;
+  }
+  void detach() {
+    s->slot[seq % kSlots].last_st = st;
+    mark_csr();  // (samplers that do not touch the CSR take their turn here)
+    released = true;
+  }
+  void release() {
+    if (released) return;
+    released = true;
+    if (!closed) abandon();
+    mark_csr();
+    mark(s->done_flag, &s->returned);
+  }
+
+ private:
+  SeqGuard(fgnn_sampler *s, uint64_t seq, hipStream_t st, bool csr_marked)
+      : s(s), seq(seq), st(st), csr_marked(csr_marked) {}
   // An early error return leaves the slot's table with this batch's pending buckets and notes: the slot's next batch
   // must not dedup against them.
   void abandon() {
@@ -353,174 +388,151 @@ struct SeqGuard {
   void mark_csr() {
     if (csr_marked) return;
     csr_marked = true;
+    mark(s->csr_flag, &s->csr_passed);
+  }
+  // this call has reached a hand-over point: `passed` moves on over every call that has, in batch order
+  void mark(bool *flag, uint64_t *passed) {
     std::lock_guard<std::mutex> lk(s->mu);
-    s->csr_flag[seq % kSlots] = true;
-    while (s->csr_flag[s->csr_passed % kSlots]) {
-      s->csr_flag[s->csr_passed % kSlots] = false;
-      ++s->csr_passed;
-    }
+    flag[seq % kSlots] = true;
+    while (flag[*passed % kSlots]) flag[(*passed)++ % kSlots] = false;
     s->cv.notify_all();
   }
-  ~SeqGuard() {
-    if (detached) return;
-    if (!finished) abandon();
-    mark_csr();
-    std::lock_guard<std::mutex> lk(s->mu);
-    s->done_flag[seq % kSlots] = true;
-    while (s->done_flag[s->returned % kSlots]) {
-      s->done_flag[s->returned % kSlots] = false;
-      ++s->returned;
-    }
-    s->cv.notify_all();
-  }
+  fgnn_sampler *s;
+  uint64_t seq;
+  hipStream_t st;
+  bool csr_marked;
+  bool closed = false;    // the success path has reset the slot's table and closed the slot itself
+  bool released = false;
 };
 
-// DoGPUSample (cuda_loops.cc:50-267) for batch `seq`.  owed_fix != null: the caller takes over the last layer's remap
-// fix-up (it lets a later launch of the batch carry it, FixTail); null: the batch's edge lists are final on return.
-//
-// Two halves.  CHAIN: everything up to and including the batch's LAST sampler launch -- for khop2, whose kernels rewrite
-// CSR rows, the part that must run in batch order on the GPU: S(L-1) -> dedup -> ... -> S(0), then the next batch's
-// S(L-1).  TAIL: the last layer's dedup fill, the fix-ups, the table's generation bump (and whatever the caller
-// appends: cache split, gather, message pack) -- nothing of the next batch waits for it.  A caller that enqueues whole
-// batches one after the other puts the next batch's chain BEHIND this batch's tail in its own enqueueing order: ~6
-// launches, 25-40 us of host time during which the GPU has finished S(0) and the chain idles (an arch5 sampler process:
-// 30 us between S(0) of batch k and S(L-1) of batch k + 1, a third of its 100 us per batch).  phase = kChain then kTail
-// (fgnn_sampler_sample_begin / _end) lets a caller enqueue chain(k + 1) BEFORE tail(k); kWhole is both, back to back.
-enum { kWhole = 0, kChain = 1, kTail = 2 };
-int sample_impl(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
-                fgnn_batch *out, void *stream, fgnn::FixTail *owed_fix, int phase = kWhole) {
-  if (owed_fix) *owed_fix = fgnn::no_fix_tail();
-  const bool do_chain = phase != kTail, do_tail = phase != kChain;
-  if (!s || !out || out->owner != s) return FGNN_EINVAL;
-  if (do_chain && ((!d_seeds && num_seeds) || num_seeds > s->cfg.max_batch_size)) return FGNN_EINVAL;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
+// A batch checks in: its arguments, then its slot, which is free once call seq - kSlots has returned (its device work
+// is ordered in sample_chain)
+int admit_batch(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds, const fgnn_batch *out) {
+  if (!s || !out || out->owner != s || (!d_seeds && num_seeds) || num_seeds > s->cfg.max_batch_size) return FGNN_EINVAL;
+  std::unique_lock<std::mutex> lk(s->mu);
+  // sequence numbers must be consecutive and used once; a gap would wait forever, so give up loudly instead
+  if (!s->cv.wait_for(lk, std::chrono::seconds(60), [&] { return seq < s->returned + kSlots; })) return FGNN_EINVAL;
+  if (seq < s->returned) return FGNN_EINVAL;
+  return FGNN_OK;
+}
+
+// FillWithDuplicates + remap of layer l; its last pass also records num_dst / num_src / num_input of the layer.
+// A layer's remap fix-up is not launched by itself: the next fill's insert launch carries it (FixTail) -- nothing of the
+// next layer's sampling reads the remapped edges -- and the last layer's goes to the caller or runs at the end.  *owed:
+// the fix-up this fill carries when called, the one it leaves on return
+int fill_layer(fgnn_sampler *s, fgnn_sampler::Slot &sl, fgnn_batch *out, hipStream_t st, long l, size_t ecap,
+               bool inserted, bool resolved, bool table_free, fgnn::FixTail *owed) {
+  size_t *d_ne = reinterpret_cast<size_t *>(&out->d_meta->num_edge[l]);
+  fgnn::FixTail mine = fgnn::no_fix_tail();
+  const int r = hashtable_fill_duplicates_ex(sl.ht, sl.tmp_dst, 0, d_ne, ecap, out->row[l], sl.ws, s->ws_bytes, st,
+                                             LayerSummary{&out->d_meta->num_dst[l], &out->d_meta->num_src[l],
+                                                          &out->d_meta->num_input},
+                                             inserted, nullptr, /*final_fill=*/l == 0, resolved, &mine, owed,
+                                             table_free && l != 0);  // (the last fill decides for itself: nothing follows it)
+  *owed = mine;
+  return r;
+}
+
+// DoGPUSample (cuda_loops.cc:50-267) for batch `seq`, in two halves.
+// CHAIN (sample_chain): everything up to and including the batch's LAST sampler launch -- for khop2, whose kernels
+// rewrite CSR rows, the part that must run in batch order on the GPU: S(L-1) -> dedup -> ... -> S(0), then the next
+// batch's S(L-1).  TAIL (sample_tail): the last layer's dedup fill, the fix-ups, the table's generation bump (and
+// whatever the caller appends: cache split, gather, message pack) -- nothing of the next batch waits for it.  A caller
+// that enqueues whole batches one after the other puts the next batch's chain BEHIND this batch's tail in its own
+// enqueueing order: ~6 launches, 25-40 us of host time during which the GPU has finished S(0) and the chain idles (an
+// arch5 sampler process: 30 us between S(0) of batch k and S(L-1) of batch k + 1, a third of its 100 us per batch).
+// fgnn_sampler_sample_begin / _end are the halves as calls of their own and let a caller enqueue chain(k + 1) BEFORE
+// tail(k); sample_batch is both, back to back.
+int sample_chain(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
+                 fgnn_batch *out, hipStream_t st, SeqGuard &guard, ChainState *cs) {
   const size_t L = s->cfg.num_layers;
   const bool mutates = s->cfg.sample_type == FGNN_KHOP2;
   const bool ordered = mutates && s->opt_unordered == 0;
   fgnn_sampler::Slot &sl = s->slot[seq % kSlots];
-  if (do_chain) {
-    // the slot is free once call seq - kSlots has returned (its device work is ordered below)
-    std::unique_lock<std::mutex> lk(s->mu);
-    // sequence numbers must be consecutive and used once; a gap would wait forever, so give up loudly instead
-    if (!s->cv.wait_for(lk, std::chrono::seconds(60), [&] { return seq < s->returned + kSlots; })) return FGNN_EINVAL;
-    if (seq < s->returned) return FGNN_EINVAL;
-  } else if (!sl.pend.active || sl.pend.seq != seq || sl.pend.out != out || sl.pend.st != st) {
-    return FGNN_EINVAL;  // no chain of this batch is waiting for its tail (on this stream)
-  }
-  SeqGuard guard{s, seq, st};
-  if (!do_chain) {
-    guard.csr_marked = true;  // (the chain half has passed the CSR on)
-    sl.pend.active = false;
-  }
   fgnn::ScanErrorSink sink(&out->d_meta->overflow);  // a timed-out cross-workgroup wait marks the batch invalid
   fgnn_hashtable *ht = sl.ht;
-  uint32_t *tmp_dst = sl.tmp_dst;
-  void *ws = sl.ws;
-  int rc = FGNN_OK;
   const bool khop_fused = s->cfg.sample_type == FGNN_KHOP2 || s->cfg.sample_type == FGNN_KHOP0;
-  // a layer's remap fix-up is not launched by itself: the next fill's insert launch carries it (FixTail) -- nothing of
-  // the next layer's sampling reads the remapped edges -- and the last layer's goes to the caller or runs at the end
-  fgnn::FixTail owed = fgnn::no_fix_tail();
-  bool ran = false, resolved0 = false, inserted0 = false;
-  size_t ecap0 = 0;
-
-  // FillWithDuplicates + remap of layer l; its last pass also records num_dst / num_src / num_input of the layer
-  auto fill = [&](long l, size_t ecap, bool inserted, bool resolved, bool table_free) -> int {
-    size_t *d_ne = reinterpret_cast<size_t *>(&out->d_meta->num_edge[l]);
-    fgnn::FixTail mine = fgnn::no_fix_tail();
-    const int r = hashtable_fill_duplicates_ex(ht, tmp_dst, 0, d_ne, ecap, out->row[l], ws, s->ws_bytes, stream,
-                                               LayerSummary{&out->d_meta->num_dst[l], &out->d_meta->num_src[l],
-                                                            &out->d_meta->num_input},
-                                               inserted, nullptr, /*final_fill=*/l == 0, resolved, &mine, &owed,
-                                               table_free && l != 0);  // (the last fill decides for itself: nothing follows it)
-    owed = mine;
-    return r;
-  };
-
-  if (do_chain) {
-    out->num_output = num_seeds;
-    out->meta_copied = false;
-    // the slot's scratch and table were last used kSlots batches ago: ordered by the stream itself when that was this
-    // stream, by the slot's event otherwise
-    sl.expect_cross = sl.was_used && sl.last_st != st;
-    // Events are recorded where the LAST hand-over crossed streams (the guess for the next one).  A hand-over that crosses
-    // without a recorded event -- a change of pattern: the pre-sampling epoch's stream -> the batch streams -- waits for
-    // the device instead.  (Until round 5 the event was recorded late on the other stream's handle, which the caller may
-    // have destroyed by then: a dangling hipStream_t is undefined behaviour, not an error return.)
-    if (sl.expect_cross) {
-      if (sl.done_recorded) FGNN_HIP_CHECK(hipStreamWaitEvent(st, sl.done, 0));
-      else FGNN_HIP_CHECK(hipDeviceSynchronize());
+  out->num_output = num_seeds;
+  out->meta_copied = false;
+  // the slot's scratch and table were last used kSlots batches ago: ordered by the stream itself when that was this
+  // stream, by the slot's event otherwise
+  sl.expect_cross = sl.was_used && sl.last_st != st;
+  // Events are recorded where the LAST hand-over crossed streams (the guess for the next one).  A hand-over that crosses
+  // without a recorded event -- a change of pattern: the pre-sampling epoch's stream -> the batch streams -- waits for
+  // the device instead.  (Until round 5 the event was recorded late on the other stream's handle, which the caller may
+  // have destroyed by then: a dangling hipStream_t is undefined behaviour, not an error return.)
+  if (sl.expect_cross) {
+    if (sl.done_recorded) FGNN_HIP_CHECK(hipStreamWaitEvent(st, sl.done, 0));
+    else FGNN_HIP_CHECK(hipDeviceSynchronize());
+  }
+  if (ordered && seq > 0) {
+    // khop2 swaps CSR entries in place: its kernels run in batch order even when batches overlap
+    {
+      std::unique_lock<std::mutex> lk(s->mu);
+      if (!s->cv.wait_for(lk, std::chrono::seconds(60), [&] { return s->csr_passed >= seq; })) return FGNN_EINVAL;
     }
-    if (ordered && seq > 0) {
-      // khop2 swaps CSR entries in place: its kernels run in batch order even when batches overlap
-      {
-        std::unique_lock<std::mutex> lk(s->mu);
-        if (!s->cv.wait_for(lk, std::chrono::seconds(60), [&] { return s->csr_passed >= seq; })) return FGNN_EINVAL;
-      }
-      fgnn_sampler::Slot &prev = s->slot[(seq - 1) % kSlots];
-      const bool cross = prev.last_st != st;
-      s->csr_cross.store(cross, std::memory_order_relaxed);  // this batch records its own hand-over if it needed one
-      if (cross) {
-        if (prev.csr_recorded) FGNN_HIP_CHECK(hipStreamWaitEvent(st, prev.csr, 0));
-        else FGNN_HIP_CHECK(hipDeviceSynchronize());  // change of pattern (see above)
-      }
+    fgnn_sampler::Slot &prev = s->slot[(seq - 1) % kSlots];
+    const bool cross = prev.last_st != st;
+    s->csr_cross.store(cross, std::memory_order_relaxed);  // this batch records its own hand-over if it needed one
+    if (cross) {
+      if (prev.csr_recorded) FGNN_HIP_CHECK(hipStreamWaitEvent(st, prev.csr, 0));
+      else FGNN_HIP_CHECK(hipDeviceSynchronize());  // change of pattern (see above)
     }
-    // new nodes are appended straight into the batch's input_nodes buffer (input_nodes = unique, cuda_loops.cc:258)
-    rc = fgnn_hashtable_set_n2o(ht, out->input_nodes);
+  }
+  // new nodes are appended straight into the batch's input_nodes buffer (input_nodes = unique, cuda_loops.cc:258)
+  int rc = fgnn_hashtable_set_n2o(ht, out->input_nodes);
+  if (rc != FGNN_OK) return rc;
+  // Reset state + FillWithUnique(seeds) + output_nodes copy + summary header: done by the first sampler launch itself
+  // for the k-hop samplers (BatchStart), by one small launch otherwise
+  const bool start_in_sampler = khop_fused && num_seeds > 0;
+  if (!start_in_sampler) {
+    rc = fgnn_hashtable_start_batch(ht, d_seeds, num_seeds, out->output_nodes, out->d_meta, batch_key, (uint32_t)L, st);
     if (rc != FGNN_OK) return rc;
-    // Reset state + FillWithUnique(seeds) + output_nodes copy + summary header: done by the first sampler launch itself
-    // for the k-hop samplers (BatchStart), by one small launch otherwise
-    const bool start_in_sampler = khop_fused && num_seeds > 0;
-    if (!start_in_sampler) {
-      rc = fgnn_hashtable_start_batch(ht, d_seeds, num_seeds, out->output_nodes, out->d_meta, batch_key, (uint32_t)L,
-                                      stream);
-      if (rc != FGNN_OK) return rc;
-    }
-    // Samplers that never look the dedup table up (all but the fused k-hop ones) may run EVERY fill through the
-    // partitioned, table-free path -- decided once per batch: if one layer's worst case is too large for it (beyond the
-    // one-launch count+assign, ~12.6 M items), a fill that fell back to the global insert would dedup against a table the
-    // earlier partitioned fills never wrote to.  Then every fill but the last takes the global path
-    bool table_free = !khop_fused;
-    for (size_t l = L, ic = num_seeds; table_free && l-- > 0;) {
-      const size_t ec = ic * s->cfg.fanout[l];
-      table_free = ec == 0 || fgnn::hashtable_can_partition(ht, ec);
-      ic += ec;
-    }
-    const uint32_t *cur = d_seeds;
-    const uint32_t *d_cur_n = nullptr;  // first layer: host count
-    size_t cur_n_host = num_seeds;
-    size_t in_cap = num_seeds;          // tighter than the create-time worst case when the batch is short
-    for (long l = (long)L - 1; l >= 0 && num_seeds; --l) {
-      const size_t fan = s->cfg.fanout[l];
-      const size_t ecap = in_cap * fan;
-      bool resolved = false, split = false;
-      size_t *d_ne = reinterpret_cast<size_t *>(&out->d_meta->num_edge[l]);
-      if (s->cfg.sample_type == FGNN_WEIGHTED_KHOP_PREFIX || s->cfg.sample_type == FGNN_KHOP1 ||
-          s->cfg.sample_type == FGNN_WEIGHTED_KHOP)
-      {
+  }
+  // Samplers that never look the dedup table up (all but the fused k-hop ones) may run EVERY fill through the
+  // partitioned, table-free path -- decided once per batch: if one layer's worst case is too large for it (beyond the
+  // one-launch count+assign, ~12.6 M items), a fill that fell back to the global insert would dedup against a table the
+  // earlier partitioned fills never wrote to.  Then every fill but the last takes the global path
+  bool table_free = !khop_fused;
+  for (size_t l = L, ic = num_seeds; table_free && l-- > 0;) {
+    const size_t ec = ic * s->cfg.fanout[l];
+    table_free = ec == 0 || fgnn::hashtable_can_partition(ht, ec);
+    ic += ec;
+  }
+  const uint32_t *cur = d_seeds;
+  const uint32_t *d_cur_n = nullptr;  // first layer: host count
+  size_t cur_n_host = num_seeds;
+  size_t in_cap = num_seeds;          // tighter than the create-time worst case when the batch is short
+  for (long l = (long)L - 1; l >= 0 && num_seeds; --l) {
+    const size_t ecap = in_cap * s->cfg.fanout[l];
+    bool resolved = false, split = false;
+    const fgnn::LayerCall call{s->cfg.indptr, s->cfg.indices, cur, cur_n_host, d_cur_n, in_cap, s->cfg.fanout[l],
+                               out->col[l], sl.tmp_dst, reinterpret_cast<size_t *>(&out->d_meta->num_edge[l]),
+                               FGNN_SRC_LOCAL, s->cfg.seed, batch_key, (uint32_t)l, sl.ws, s->ws_bytes, st};
+    switch (s->cfg.sample_type) {
+      case FGNN_WEIGHTED_KHOP_PREFIX:
+      case FGNN_KHOP1:
+      case FGNN_WEIGHTED_KHOP: {
         // the frontier is a list of unique node ids: seed order by bitmap ranking, no sort (sample_weighted.hip)
         // FGNN_RANK_BITMAP=0 (profiling build, A/B only): order the seeds with scan.hip's sort like the stateless
         // C entry points
         static const bool use_rank = fgnn::tune_int("FGNN_RANK_BITMAP", 1) != 0;
         const fgnn::RankWs rank{use_rank ? sl.rank_bitmap : nullptr, &sl.scan_sample};
-        rc = fgnn::sample_with_replacement_ex(
-            s->cfg.sample_type, s->cfg.indptr, s->cfg.indices,
+        rc = fgnn::sample_with_replacement(
+            call, s->cfg.sample_type,
             s->cfg.sample_type == FGNN_WEIGHTED_KHOP_PREFIX ? s->cfg.prob_prefix : s->cfg.prob_table, s->cfg.alias_table,
-            cur, cur_n_host, d_cur_n, in_cap, fan, out->col[l], tmp_dst, d_ne, FGNN_SRC_LOCAL, s->cfg.seed, batch_key,
-            (uint32_t)l, ws, s->ws_bytes, stream, s->cfg.num_node, rank.bitmap ? &rank : nullptr,
-            fgnn::prefix_tree_view(s->ptree));
+            s->cfg.num_node, rank.bitmap ? &rank : nullptr, fgnn::prefix_tree_view(s->ptree));
+        break;
       }
-      else if (s->cfg.sample_type == FGNN_WEIGHTED_KHOP_HASH_DEDUP)
-        rc = fgnn::sample_hash_dedup(s->cfg.indptr, s->cfg.indices, s->cfg.prob_table, s->cfg.alias_table, cur,
-                                     cur_n_host, d_cur_n, in_cap, fan, out->col[l], tmp_dst, d_ne, FGNN_SRC_LOCAL,
-                                     s->cfg.seed, batch_key, (uint32_t)l, ws, s->ws_bytes, stream, &sl.scan_sample);
-      else if (s->cfg.sample_type == FGNN_RANDOM_WALK)
+      case FGNN_WEIGHTED_KHOP_HASH_DEDUP:
+        rc = fgnn::sample_hash_dedup(call, s->cfg.prob_table, s->cfg.alias_table, &sl.scan_sample);
+        break;
+      case FGNN_RANDOM_WALK:
         // fanout[l] == RunConfig::num_neighbor (CHECK_EQ at cuda_loops.cc:129)
-        rc = fgnn::sample_random_walk_ex(s->cfg.indptr, s->cfg.indices, cur, cur_n_host, d_cur_n, in_cap, s->cfg.walk_len,
-                                         s->cfg.restart_prob, s->cfg.num_walks, fan, out->col[l], tmp_dst, out->data[l],
-                                         d_ne, FGNN_SRC_LOCAL, s->cfg.seed, batch_key, (uint32_t)l, ws, s->ws_bytes,
-                                         stream, &sl.scan_sample);
-      else {
+        rc = fgnn::sample_random_walk(call, s->cfg.walk_len, s->cfg.restart_prob, s->cfg.num_walks, out->data[l],
+                                      &sl.scan_sample);
+        break;
+      default: {
         // k-hop: the sampler inserts every edge it emits into the dedup table itself (pass 1 of FillWithDuplicates)
         const fgnn::BatchStart start{ht->n2o, out->output_nodes, out->d_meta, batch_key, (uint32_t)L, (uint32_t)l};
         const bool first = start_in_sampler && l == (long)L - 1;
@@ -532,73 +544,53 @@ int sample_impl(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t n
         // and one re-read of the layer's neighbour list; profiles/r02_split_ab.txt).  Not when this launch also inserts
         // the seeds: their local ids would replace pending edges without a note.
         split = ordered && l == 0 && !first && s->opt_split_l0 != 0;
-        if (split)
-          rc = fgnn::sample_khop_plain(mutates, s->cfg.indptr, s->cfg.indices, cur, cur_n_host, d_cur_n, in_cap, fan,
-                                       out->col[l], tmp_dst, d_ne, s->cfg.seed, batch_key, (uint32_t)l, ws, s->ws_bytes,
-                                       stream, &sl.scan_sample);
-        else {
-          // last fill of the batch: the insert hands its outcome to the dedup pass, which then never touches the table
-          resolved = l == 0 && !first && fgnn::hashtable_can_resolve(ht, ecap);
-          rc = sample_khop_fused(mutates, s->cfg.indptr, s->cfg.indices, cur, cur_n_host, d_cur_n, in_cap, fan,
-                                 out->col[l], tmp_dst, d_ne, s->cfg.seed, batch_key, (uint32_t)l, ht, ws, s->ws_bytes,
-                                 stream, &sl.scan_sample, first ? &start : nullptr, resolved);
-        }
+        // last fill of the batch: the insert hands its outcome to the dedup pass, which then never touches the table
+        resolved = !split && l == 0 && !first && fgnn::hashtable_can_resolve(ht, ecap);
+        rc = fgnn::sample_khop(call, mutates, split ? nullptr : ht, first ? &start : nullptr, resolved,
+                               &sl.scan_sample);
       }
-      if (rc != FGNN_OK) return rc;
-      const bool inserted = khop_fused && !split;
-      if (l == 0) {
-        // last sampler kernel of this batch: the next batch may touch the CSR; the layer's fill belongs to the tail
-        if (mutates) guard.pass_csr(true);
-        ran = true;
-        ecap0 = ecap;
-        resolved0 = resolved;
-        inserted0 = inserted;
-        break;
-      }
-      rc = fill(l, ecap, inserted, resolved, table_free);
-      if (rc != FGNN_OK) return rc;
-      in_cap += ecap;
-      cur = out->input_nodes;
-      d_cur_n = fgnn_hashtable_d_num_items(ht);
-      cur_n_host = 0;
     }
-    if (mutates) guard.pass_csr(true);  // (a batch without seeds still takes its turn)
-    if (!do_tail) {
-      sl.pend.active = true;
-      sl.pend.seq = seq;
-      sl.pend.out = out;
-      sl.pend.ran = ran;
-      sl.pend.ecap0 = ecap0;
-      sl.pend.resolved0 = resolved0;
-      sl.pend.inserted0 = inserted0;
-      sl.pend.owed = owed;
-      sl.pend.st = st;
-      sl.last_st = st;
-      guard.mark_csr();  // (samplers that do not touch the CSR take their turn here)
-      guard.detached = true;
-      return launch_status(__func__);
+    if (rc != FGNN_OK) return rc;
+    const bool inserted = khop_fused && !split;
+    if (l == 0) {
+      // last sampler kernel of this batch: the next batch may touch the CSR; the layer's fill belongs to the tail
+      if (mutates) guard.pass_csr(true);
+      cs->ran = true;
+      cs->ecap0 = ecap;
+      cs->resolved0 = resolved;
+      cs->inserted0 = inserted;
+      break;
     }
-  } else {
-    ran = sl.pend.ran;
-    ecap0 = sl.pend.ecap0;
-    resolved0 = sl.pend.resolved0;
-    inserted0 = sl.pend.inserted0;
-    owed = sl.pend.owed;
+    rc = fill_layer(s, sl, out, st, l, ecap, inserted, resolved, table_free, &cs->owed);
+    if (rc != FGNN_OK) return rc;
+    in_cap += ecap;
+    cur = out->input_nodes;
+    d_cur_n = fgnn_hashtable_d_num_items(ht);
+    cur_n_host = 0;
   }
-  // ---- tail
-  if (ran) {
-    rc = fill(0, ecap0, inserted0, resolved0, false);
+  if (mutates) guard.pass_csr(true);  // (a batch without seeds still takes its turn)
+  return FGNN_OK;
+}
+
+// owed_fix != null: the caller takes over the last layer's remap fix-up (it lets a later launch of the batch carry it,
+// FixTail); null: the batch's edge lists are final on return
+int sample_tail(fgnn_sampler *s, uint64_t seq, fgnn_batch *out, hipStream_t st, SeqGuard &guard, ChainState cs,
+                fgnn::FixTail *owed_fix) {
+  fgnn_sampler::Slot &sl = s->slot[seq % kSlots];
+  fgnn::ScanErrorSink sink(&out->d_meta->overflow);
+  int rc = FGNN_OK;
+  if (cs.ran) {
+    rc = fill_layer(s, sl, out, st, 0, cs.ecap0, cs.inserted0, cs.resolved0, false, &cs.owed);
     if (rc != FGNN_OK) return rc;
   }
-  if (owed.mapped) {
-    if (owed_fix) *owed_fix = owed;
-    else if ((rc = fgnn::hashtable_map_fix(owed, stream)) != FGNN_OK) return rc;
+  if (cs.owed.mapped) {
+    if (owed_fix) *owed_fix = cs.owed;
+    else if ((rc = fgnn::hashtable_map_fix(cs.owed, st)) != FGNN_OK) return rc;
   }
   // Reset (cuda_hashtable.cu:714-723) for the slot's next batch: a generation bump, no memory traffic
-  rc = fgnn::hashtable_next_generation(ht, stream, false);
+  rc = fgnn::hashtable_next_generation(sl.ht, st, false);
   if (rc != FGNN_OK) return rc;
   guard.close_slot();
-  guard.finished = true;
   return launch_status(__func__);
 }
 
@@ -612,51 +604,83 @@ int batch_cache_index(fgnn_batch *b, const uint32_t *cache_table, void *stream, 
                                        reinterpret_cast<unsigned long long *>(&b->d_meta->t_sampled), carry);
 }
 
+// The tail of a batch whose chain is enqueued, then [cache_table != null] DoGetCacheMissIndex: with a cache split to
+// follow, the last layer's remap fix-up rides on that launch.  The call has returned, as far as later calls are
+// concerned, when the tail is enqueued.
+int finish_sampling(fgnn_sampler *s, uint64_t seq, fgnn_batch *out, const uint32_t *cache_table, hipStream_t st,
+                    SeqGuard &guard, const ChainState &cs) {
+  fgnn::FixTail owed = fgnn::no_fix_tail();
+  int rc = sample_tail(s, seq, out, st, guard, cs, cache_table ? &owed : nullptr);
+  guard.release();
+  if (rc == FGNN_OK && cache_table) rc = batch_cache_index(out, cache_table, st, &owed);
+  return rc;
+}
+
+// a whole batch: chain and tail back to back [+ the cache split]
+int sample_batch(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
+                 fgnn_batch *out, const uint32_t *cache_table, void *stream) {
+  int rc = admit_batch(s, seq, d_seeds, num_seeds, out);
+  if (rc != FGNN_OK) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  SeqGuard guard = SeqGuard::for_chain(s, seq, st);
+  ChainState cs;
+  rc = sample_chain(s, seq, d_seeds, num_seeds, batch_key, out, st, guard, &cs);
+  return rc == FGNN_OK ? finish_sampling(s, seq, out, cache_table, st, guard, cs) : rc;
+}
+
 }  // namespace
 
 extern "C" int fgnn_sampler_sample_ordered(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds,
                                            uint64_t batch_key, fgnn_batch *out, void *stream) {
-  return sample_impl(s, seq, d_seeds, num_seeds, batch_key, out, stream, nullptr);
+  return sample_batch(s, seq, d_seeds, num_seeds, batch_key, out, nullptr, stream);
 }
 
 extern "C" int fgnn_sampler_sample(fgnn_sampler *s, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
                                    fgnn_batch *out, void *stream) {
   if (!s) return FGNN_EINVAL;
-  uint64_t seq;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    seq = s->next_seq++;
-  }
-  return fgnn_sampler_sample_ordered(s, seq, d_seeds, num_seeds, batch_key, out, stream);
+  return sample_batch(s, take_seq(s), d_seeds, num_seeds, batch_key, out, nullptr, stream);
 }
 
-// the two halves of a batch as calls of their own (sample_impl): a caller with several batches in flight enqueues
-// begin(k + 1) BEFORE end(k), so that khop2's cross-batch sampler chain never waits for the host to get through a
-// batch's tail.  end = the tail [+ the cache-index split, which carries the last remap fix-up]; the caller then appends
+// the two halves of a batch as calls of their own (sample_chain / sample_tail): a caller with several batches in flight
+// enqueues begin(k + 1) BEFORE end(k), so that khop2's cross-batch sampler chain never waits for the host to get through
+// a batch's tail.  end = the tail [+ the cache-index split, which carries the last remap fix-up]; the caller then appends
 // extraction / message pack and fgnn_batch_finish on the same stream.
+extern "C" int fgnn_sampler_sample_begin_ordered(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds,
+                                                 size_t num_seeds, uint64_t batch_key, fgnn_batch *out, void *stream) {
+  int rc = admit_batch(s, seq, d_seeds, num_seeds, out);
+  if (rc != FGNN_OK) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  SeqGuard guard = SeqGuard::for_chain(s, seq, st);
+  ChainState cs;
+  rc = sample_chain(s, seq, d_seeds, num_seeds, batch_key, out, st, guard, &cs);
+  if (rc != FGNN_OK) return rc;
+  fgnn_sampler::Slot::Pend &pend = s->slot[seq % kSlots].pend;
+  pend.active = true;
+  pend.seq = seq;
+  pend.out = out;
+  pend.st = st;
+  pend.chain = cs;
+  guard.detach();
+  return launch_status(__func__);
+}
+
 extern "C" int fgnn_sampler_sample_begin(fgnn_sampler *s, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
                                          fgnn_batch *out, void *stream, uint64_t *seq_out) {
   if (!s || !seq_out) return FGNN_EINVAL;
-  uint64_t seq;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    seq = s->next_seq++;
-  }
-  *seq_out = seq;
-  return sample_impl(s, seq, d_seeds, num_seeds, batch_key, out, stream, nullptr, kChain);
-}
-
-extern "C" int fgnn_sampler_sample_begin_ordered(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds,
-                                                 size_t num_seeds, uint64_t batch_key, fgnn_batch *out, void *stream) {
-  return sample_impl(s, seq, d_seeds, num_seeds, batch_key, out, stream, nullptr, kChain);
+  *seq_out = take_seq(s);
+  return fgnn_sampler_sample_begin_ordered(s, *seq_out, d_seeds, num_seeds, batch_key, out, stream);
 }
 
 extern "C" int fgnn_sampler_sample_end(fgnn_sampler *s, uint64_t seq, fgnn_batch *out, const uint32_t *cache_table,
                                        void *stream) {
-  fgnn::FixTail owed = fgnn::no_fix_tail();
-  int rc = sample_impl(s, seq, nullptr, 0, 0, out, stream, cache_table ? &owed : nullptr, kTail);
-  if (rc == FGNN_OK && cache_table) rc = batch_cache_index(out, cache_table, stream, &owed);
-  return rc;
+  if (!s || !out || out->owner != s) return FGNN_EINVAL;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  fgnn_sampler::Slot::Pend &pend = s->slot[seq % kSlots].pend;
+  // no chain of this batch is waiting for its tail (on this stream)
+  if (!pend.active || pend.seq != seq || pend.out != out || pend.st != st) return FGNN_EINVAL;
+  SeqGuard guard = SeqGuard::for_tail(s, seq, st);
+  pend.active = false;
+  return finish_sampling(s, seq, out, cache_table, st, guard, pend.chain);
 }
 
 // DoGPUSample + DoGetCacheMissIndex (dist_loops_arch5.cc:86-105: what an arch5 sampler does per batch) in one call, with
@@ -665,25 +689,14 @@ extern "C" int fgnn_sampler_sample_indexed(fgnn_sampler *s, const uint32_t *d_se
                                            uint64_t batch_key, fgnn_batch *out, const uint32_t *cache_table,
                                            void *stream) {
   if (!s) return FGNN_EINVAL;
-  uint64_t seq;
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    seq = s->next_seq++;
-  }
-  fgnn::FixTail owed = fgnn::no_fix_tail();
-  int rc = sample_impl(s, seq, d_seeds, num_seeds, batch_key, out, stream, cache_table ? &owed : nullptr);
-  if (rc == FGNN_OK && cache_table) rc = batch_cache_index(out, cache_table, stream, &owed);
-  return rc;
+  return sample_batch(s, take_seq(s), d_seeds, num_seeds, batch_key, out, cache_table, stream);
 }
 
 // whole batch in one call: sample -> [cache index] -> extract -> summary copy (saves host round trips per step)
 extern "C" int fgnn_sampler_run_batch(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds,
                                       uint64_t batch_key, fgnn_batch *out, const uint32_t *cache_table,
                                       const void *feat, const void *label, void *stream) {
-  fgnn::FixTail owed = fgnn::no_fix_tail();
-  // with a cache split to follow, the last layer's remap fix-up rides on that launch
-  int rc = sample_impl(s, seq, d_seeds, num_seeds, batch_key, out, stream, cache_table ? &owed : nullptr);
-  if (rc == FGNN_OK && cache_table) rc = batch_cache_index(out, cache_table, stream, &owed);
+  int rc = sample_batch(s, seq, d_seeds, num_seeds, batch_key, out, cache_table, stream);
   if (rc == FGNN_OK && (feat || label)) rc = fgnn_batch_extract(out, feat, label, stream);
   if (rc == FGNN_OK) rc = fgnn_batch_finish(out, stream);
   return rc;
@@ -777,6 +790,19 @@ bool make_tail(fgnn_batch *b, const void *src, const void *label, fgnn::GatherTa
   return true;
 }
 
+// room for `slots` workgroups' start / end clock words in the batch's stamp buffer -- pinned host memory: every
+// workgroup posts its two words there, no copy behind the launch
+int ensure_stamps(fgnn_batch *b, size_t slots) {
+  if (slots <= b->stamp_cap) return FGNN_OK;
+  if (b->h_stamps) (void)hipHostFree(b->h_stamps);
+  b->h_stamps = nullptr;
+  b->stamp_cap = 0;
+  FGNN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&b->h_stamps), 2 * slots * sizeof(unsigned long long),
+                               hipHostMallocDefault));
+  b->stamp_cap = slots;
+  return FGNN_OK;
+}
+
 }  // namespace
 
 extern "C" int fgnn_batch_extract(fgnn_batch *b, const void *feat, const void *label, void *stream) {
@@ -793,14 +819,7 @@ extern "C" int fgnn_batch_extract(fgnn_batch *b, const void *feat, const void *l
     if (b->timing && tailed) {
       // the launch's own duration from its workgroups' clock words (pinned memory), next to the HIP-event bracket: the
       // events also hold the launch gap and the wait for wave slots behind other batches' kernels
-      if (b->stamp_cap < fgnn::kGatherStampBlocks + 1) {
-        if (b->h_stamps) (void)hipHostFree(b->h_stamps);
-        b->h_stamps = nullptr;
-        b->stamp_cap = 0;
-        FGNN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&b->h_stamps),
-                                     2 * (fgnn::kGatherStampBlocks + 1) * sizeof(unsigned long long), hipHostMallocDefault));
-        b->stamp_cap = fgnn::kGatherStampBlocks + 1;
-      }
+      if ((rc = ensure_stamps(b, fgnn::kGatherStampBlocks + 1)) != FGNN_OK) return rc;
       b->h_stamps[2 * fgnn::kGatherStampBlocks] = 0;
       tail.stamps = b->h_stamps;
       b->stamped = true;
@@ -850,16 +869,7 @@ extern "C" int fgnn_batch_extract_cached(fgnn_batch *b, const void *cache_rows, 
   if (full_feat && cache_rows && tailed && fgnn::extract_can_fuse(job)) {
     job.link_wgs = fgnn::pointer_is_host(full_feat) ? FGNN_LINK_WGS_SHARED : 0;  // this GPU samples too
     if (timing) {
-      const size_t grid = fgnn::extract_fused_grid(job);
-      if (grid > b->stamp_cap) {
-        if (b->h_stamps) (void)hipHostFree(b->h_stamps);
-        b->h_stamps = nullptr;
-        b->stamp_cap = 0;
-        // pinned host memory: every workgroup posts its two clock words there, no copy behind the launch
-        FGNN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&b->h_stamps), 2 * grid * sizeof(unsigned long long),
-                                     hipHostMallocDefault));
-        b->stamp_cap = grid;
-      }
+      if ((rc = ensure_stamps(b, fgnn::extract_fused_grid(job))) != FGNN_OK) return rc;
       job.stamps = b->h_stamps;
       FGNN_HIP_CHECK(hipEventRecord(b->t0, st));
     }
@@ -904,9 +914,7 @@ extern "C" int fgnn_sampler_run_batch_cached(fgnn_sampler *s, uint64_t seq, cons
                                              const void *cache_rows, const void *full_feat, const void *label,
                                              void *stream) {
   if (!cache_table) return FGNN_EINVAL;
-  fgnn::FixTail owed = fgnn::no_fix_tail();
-  int rc = sample_impl(s, seq, d_seeds, num_seeds, batch_key, out, stream, &owed);
-  if (rc == FGNN_OK) rc = batch_cache_index(out, cache_table, stream, &owed);
+  int rc = sample_batch(s, seq, d_seeds, num_seeds, batch_key, out, cache_table, stream);
   if (rc == FGNN_OK) rc = fgnn_batch_extract_cached(out, cache_rows, full_feat, label, stream);
   if (rc == FGNN_OK) rc = fgnn_batch_finish(out, stream);
   return rc;
@@ -940,7 +948,7 @@ extern "C" int fgnn_sampler_run_range(fgnn_sampler *s, const fgnn_run_plan *p, u
     return FGNN_OK;
   };
   int rc = FGNN_OK;
-  // chain(i) is enqueued BEFORE tail(i - 1) (sample_impl): with whole batches enqueued one after the other the next
+  // chain(i) is enqueued BEFORE tail(i - 1) (sample_chain): with whole batches enqueued one after the other the next
   // batch's first sampler launch sits behind ~6 launches of this batch's tail in the host's order, and on a slow host
   // khop2's cross-batch chain waits for the host, not for the GPU.  Needs a second buffer (the tail of batch i - 1 is
   // still owed when batch i starts)

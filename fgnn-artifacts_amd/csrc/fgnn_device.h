@@ -461,6 +461,17 @@ __device__ __forceinline__ uint32_t scan_lookback(const ScanWs &w, uint32_t tile
   return scan_prefix(w, tile, sh);
 }
 
+// Largest grid of a single-pass kernel: every tile reads ALL its predecessors' descriptors (scan_prefix), O(tiles^2)
+// loads in total, and every workgroup of the grid may wait for another -- 192 workgroups per XCD.  A launcher whose job
+// needs more tiles gives each thread more items (single_pass_items_per_thread) or takes count -> one-workgroup scan ->
+// consumer instead.
+constexpr size_t kSinglePassMaxTiles = 1536;
+// items per thread at which a job of `nb` one-item-per-thread workgroups fits a single-pass grid (the emit kernels are
+// built for 1, 4 and 16); 0: it does not fit
+inline int single_pass_items_per_thread(size_t nb) {
+  return nb <= kSinglePassMaxTiles ? 1 : nb <= 4 * kSinglePassMaxTiles ? 4 : nb <= 16 * kSinglePassMaxTiles ? 16 : 0;
+}
+
 // polls of one descriptor before a waiter starts helping: ~1 us per poll (load round trip + sleep) -- an order of
 // magnitude above the longest wait of a healthy launch (predecessors publish within microseconds of starting), so the
 // helping path only runs when predecessors are not resident
@@ -788,12 +799,6 @@ int get_miss_cache_index_ex(const uint32_t *table, const uint32_t *nodes, size_t
                             uint32_t *cache_src, uint32_t *cache_dst, uint32_t *d_counts, void *ws, size_t ws_bytes,
                             void *stream, ScanWsHost *scan, unsigned long long *stamp = nullptr,
                             const FixTail *carry_fix = nullptr);
-// fgnn_sample_weighted_khop_hash_dedup with the slot's look-back descriptors (scan == null: descriptors in ws)
-int sample_hash_dedup(const uint32_t *indptr, const uint32_t *indices, const float *prob_table,
-                      const uint32_t *alias_table, const uint32_t *input, size_t num_input, const uint32_t *d_num_input,
-                      size_t num_input_cap, size_t fanout, uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out,
-                      int src_mode, uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes,
-                      void *stream, ScanWsHost *scan_host);
 // 5-ary search trees over the long rows of a prefix-sum table (prefix_tree.hip): tree_off[row] = node index of the
 // row's root in `pool` (4 floats per node), FGNN_EMPTY_KEY for rows without a tree (short, or not non-decreasing)
 constexpr uint32_t kPrefixTreeMinLen = 64;
@@ -822,41 +827,69 @@ struct BatchStart {
   uint32_t num_layers;
   uint32_t layer;  // this launch's layer: its num_edge entry is written by the launch itself, not by the header init
 };
-// the three with-replacement samplers (khop1 / weighted_khop / weighted_khop_prefix by sample_type; table_f = prob or
-// prefix table) for callers that know the number of graph nodes, guarantee unique seeds and own a RankWs: the seed
-// order then comes from a bitmap over the id space instead of a radix sort (sample_weighted.hip) -- no library call.
-// rank == null: as the C entry points (scan.hip's sort orders the seeds).  Scratch: fgnn_weighted_scratch_bytes.
+// with-replacement samplers: seed ranking bitmap over the node ids of a caller that knows the number of graph nodes and
+// guarantees unique seeds (sample_with_replacement)
 struct RankWs {
   uint32_t *bitmap;   // rank_ws_bytes(num_node) bytes, ALL ZERO between calls (the call restores that): bitmap | pre | sums
   ScanWsHost *scan;   // look-back descriptors for the two single-pass launches
 };
 size_t rank_ws_bytes(size_t num_node);
-int sample_with_replacement_ex(int sample_type, const uint32_t *indptr, const uint32_t *indices, const float *table_f,
-                               const uint32_t *alias, const uint32_t *input, size_t num_input,
-                               const uint32_t *d_num_input, size_t num_input_cap, size_t fanout, uint32_t *out_src,
-                               uint32_t *out_dst, size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key,
-                               uint32_t layer, void *ws, size_t ws_bytes, void *stream, size_t num_node,
-                               const RankWs *rank, PrefixTreeView tree = PrefixTreeView{nullptr, nullptr, nullptr});
-// fgnn_sample_random_walk with look-back descriptors: the edge offsets and the compacted output come from one launch
-// (scan == null: per-workgroup sums -> scan -> emit, as the C entry point)
-int sample_random_walk_ex(const uint32_t *indptr, const uint32_t *indices, const uint32_t *input, size_t num_input,
-                          const uint32_t *d_num_input, size_t num_input_cap, size_t walk_len, double restart_prob,
-                          size_t num_walks, size_t K, uint32_t *out_src, uint32_t *out_dst, uint32_t *out_data,
-                          size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws,
-                          size_t ws_bytes, void *stream, ScanWsHost *scan);
-// k-hop sampling with the dedup insert fused into the sampler (the engine's path): as fgnn_sample_khop0/2
-// with FGNN_SRC_LOCAL, and every emitted edge e is inserted into `ht` with value PENDING|e; its bucket goes
-// to ws[e] (the pos[] array hashtable_fill_duplicates_ex(already_inserted = true) expects at ws).
-int sample_khop_fused(bool khop2, const uint32_t *indptr, uint32_t *indices, const uint32_t *input, size_t num_input,
-                      const uint32_t *d_num_input, size_t cap, size_t fanout, uint32_t *out_src, uint32_t *out_dst,
-                      size_t *d_num_out, uint64_t seed, uint64_t batch_key, uint32_t layer, fgnn_hashtable *ht,
-                      void *ws, size_t ws_bytes, void *stream, ScanWsHost *scan, const BatchStart *start = nullptr,
-                      bool resolve = false);
-int sample_khop_plain(bool khop2, const uint32_t *indptr, uint32_t *indices, const uint32_t *input, size_t num_input,
-                      const uint32_t *d_num_input, size_t cap, size_t fanout, uint32_t *out_src, uint32_t *out_dst,
-                      size_t *d_num_out, uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes,
-                      void *stream, ScanWsHost *scan);
+
+// "Sample one layer": what every sampler takes, whichever it is -- the arguments the fgnn_sample_* entry points of
+// fgnn_hip.h have in common, under the same names and with the same meaning.  The C entry points and the batch driver
+// fill one per call; each sampler has ONE launcher, which takes it plus only what is its own.
+struct LayerCall {
+  const uint32_t *indptr;
+  uint32_t *indices;              // not const: khop2 swaps the entries of the rows it draws from
+  const uint32_t *input;          // the frontier
+  size_t num_input;               // host count, used when d_num_input == null
+  const uint32_t *d_num_input;    // device count
+  size_t cap;                     // capacity of `input` under a device count (num_input_cap)
+  size_t fanout;                  // random walk: K, the neighbours kept per seed
+  uint32_t *out_src, *out_dst;    // COO, fanout entries per seed at most
+  size_t *d_num_out;              // device: edges emitted (nullable)
+  int src_mode;                   // FGNN_SRC_GLOBAL / FGNN_SRC_LOCAL
+  uint64_t seed, batch_key;       // the draw address: Philox key, ...
+  uint32_t layer;                 // ... and the low byte of its tag
+  void *ws;                       // scratch, ws_bytes of it: at least the sampler's own fgnn_*_scratch_bytes
+  size_t ws_bytes;
+  hipStream_t stream;
+};
+// What every launcher does first, between its own fanout checks and its null / size checks: the frontier's capacity
+// (the host count unless there is a device count), the Philox tag of (sample type, layer), and the empty call --
+// nothing to launch, the count word zeroed: `rc` is then the call's result
+struct LayerPrologue { size_t cap; uint32_t tag; bool empty; int rc; };
+inline int zero_count(size_t *d_num_out, hipStream_t stream) {
+  if (d_num_out) FGNN_HIP_CHECK(hipMemsetAsync(d_num_out, 0, sizeof(size_t), stream));
+  return FGNN_OK;
+}
+inline LayerPrologue layer_prologue(const LayerCall &c, int sample_type) {
+  const size_t cap = c.d_num_input ? c.cap : c.num_input;
+  return LayerPrologue{cap, ((uint32_t)sample_type << 8) | (c.layer & 0xffu), cap == 0,
+                       cap == 0 ? zero_count(c.d_num_out, c.stream) : FGNN_OK};
+}
+
+// fgnn_sample_khop0 / _khop2.  ht != null (the batch driver's path): the dedup insert is fused into the sampler --
+// every emitted edge e is inserted into `ht` with value PENDING|e, its bucket goes to ws[e] (the pos[] array
+// hashtable_fill_duplicates_ex(already_inserted = true) expects at ws); `start`: the launch is the batch's first.
+// ht == null: the sampler alone (with `scan`: the driver's split last layer -- khop2's CSR-order chain then ends with
+// this kernel, the dedup insert runs behind it).  scan: the slot's look-back descriptors, one launch.
 // resolve: the fill is the batch's last (hashtable_fill_duplicates_ex(..., final_fill, resolved = true) must follow):
 // ws[e] receives the insert's OUTCOME (ht_insert_resolve) instead of the bucket.  Needs ht->disp.
+int sample_khop(const LayerCall &c, bool khop2, fgnn_hashtable *ht = nullptr, const BatchStart *start = nullptr,
+                bool resolve = false, ScanWsHost *scan = nullptr);
+// fgnn_sample_khop1 / _weighted_khop / _weighted_khop_prefix by sample_type (table_f = prob or prefix table).  rank !=
+// null: the caller knows the number of graph nodes, guarantees unique seeds and owns a RankWs -- the seed order then
+// comes from a bitmap over the id space instead of a radix sort (sample_weighted.hip), no library call; null:
+// scan.hip's sort orders the seeds.  tree: weighted_khop_prefix only.  Scratch: fgnn_weighted_scratch_bytes.
+int sample_with_replacement(const LayerCall &c, int sample_type, const float *table_f, const uint32_t *alias,
+                            size_t num_node = 0, const RankWs *rank = nullptr,
+                            PrefixTreeView tree = PrefixTreeView{nullptr, nullptr, nullptr});
+// fgnn_sample_weighted_khop_hash_dedup; scan: the slot's look-back descriptors (null: descriptors in ws)
+int sample_hash_dedup(const LayerCall &c, const float *prob_table, const uint32_t *alias_table, ScanWsHost *scan);
+// fgnn_sample_random_walk (K = c.fanout); scan: look-back descriptors -- the edge offsets and the compacted output then
+// come from one launch (null: per-workgroup sums -> scan -> emit)
+int sample_random_walk(const LayerCall &c, size_t walk_len, double restart_prob, size_t num_walks, uint32_t *out_data,
+                       ScanWsHost *scan);
 
 }  // namespace fgnn

@@ -558,7 +558,7 @@ int fgnn::hashtable_fill_duplicates_ex(fgnn_hashtable *ht, const uint32_t *items
   if (!ht) return FGNN_EINVAL;
   if (owed_fix) *owed_fix = no_fix_tail();  // mapped != null on return: the caller owes this fill's fix-up
   FixTail carry = carry_fix && carry_fix->mapped ? *carry_fix : no_fix_tail();
-  // resolved: pos[] holds insert outcomes (sample_khop_fused(..., resolve = true)); only the one-launch path reads them
+  // resolved: pos[] holds insert outcomes (sample_khop(..., resolve = true)); only the one-launch path reads them
   if (resolved && !(already_inserted && final_fill && mapped && ht->disp)) return FGNN_EINVAL;
   if (!scan) scan = ht->scan;  // hashtable_can_resolve looks at ht->scan: the descriptors used must be those
   size_t cap = d_num_items ? num_items_cap : num_items;

@@ -11,14 +11,13 @@
 // seed live in LDS (column `lane` of sel[fanout][256], conflict-free), where the rejection test scans them and
 // from where they are emitted -- no padded temporaries, no count / scan / compact kernels: the output offset of a
 // workgroup comes from the cross-workgroup prefix of fgnn_device.h (a workgroup waits only for lower-numbered ones,
-// which were dispatched before it: safe next to other streams' kernels).  Frontiers of more than kMaxScanTiles
+// which were dispatched before it: safe next to other streams' kernels).  Frontiers of more than kSinglePassMaxTiles
 // workgroups take two launches of the same kernel instead (count, one-workgroup scan, emit).
 #include "fgnn_device.h"
 
 namespace fgnn {
 namespace {
 
-constexpr uint32_t kMaxScanTiles = 1536;  // cap of every waiting grid (fgnn_device.h): 192 workgroups per XCD
 constexpr uint32_t kMaxFanout = 50;  // the reference's per-thread table has 50 slots (hash_dedup.cu:43,72)
 __host__ __device__ constexpr uint32_t max_attempts(uint32_t fanout) { return 64u * fanout; }
 
@@ -96,27 +95,23 @@ __global__ __launch_bounds__(kBlock) void hash_dedup_kernel(const uint32_t *__re
 
 }  // namespace
 
-int sample_hash_dedup(const uint32_t *indptr, const uint32_t *indices, const float *prob_table,
-                      const uint32_t *alias_table, const uint32_t *input, size_t num_input, const uint32_t *d_num_input,
-                      size_t num_input_cap, size_t fanout, uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out,
-                      int src_mode, uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes,
-                      void *stream, ScanWsHost *scan_host) {
-  auto st = static_cast<hipStream_t>(stream);
-  size_t cap = d_num_input ? num_input_cap : num_input;
-  if (fanout == 0 || fanout > kMaxFanout) return FGNN_EINVAL;
-  if (cap == 0) {
-    if (d_num_out) FGNN_HIP_CHECK(hipMemsetAsync(d_num_out, 0, sizeof(size_t), st));
-    return FGNN_OK;
-  }
-  if (!indptr || !indices || !prob_table || !alias_table || !input || cap * fanout >= 0x7fffffffull) return FGNN_EINVAL;
-  const uint32_t F = (uint32_t)fanout;
-  const uint32_t tag = ((uint32_t)FGNN_WEIGHTED_KHOP_HASH_DEDUP << 8) | (layer & 0xffu);
+int sample_hash_dedup(const LayerCall &c, const float *prob_table, const uint32_t *alias_table, ScanWsHost *scan_host) {
+  if (c.fanout == 0 || c.fanout > kMaxFanout) return FGNN_EINVAL;
+  const LayerPrologue pro = layer_prologue(c, FGNN_WEIGHTED_KHOP_HASH_DEDUP);
+  if (pro.empty) return pro.rc;
+  const size_t cap = pro.cap;
+  if (!c.indptr || !c.indices || !prob_table || !alias_table || !c.input || cap * c.fanout >= 0x7fffffffull)
+    return FGNN_EINVAL;
+  const uint32_t F = (uint32_t)c.fanout;
+  const hipStream_t st = c.stream;
+  void *const ws = c.ws;
+  const size_t ws_bytes = c.ws_bytes;
   const size_t lds = (size_t)F * kBlock * sizeof(uint32_t);
   const size_t nb = div_up(cap, (size_t)kBlock);
   ScanWs scan{nullptr, nullptr, 0, 0, nullptr, nullptr, 0, kScanHelpAfterPolls, nullptr};
   uint32_t *sums = nullptr;
   int mode = 0;
-  if (nb > kMaxScanTiles) {
+  if (nb > kSinglePassMaxTiles) {
     if (ws_bytes < (nb + 2) * sizeof(uint32_t)) return FGNN_ENOSPC;
     sums = static_cast<uint32_t *>(ws);
     mode = 1;
@@ -138,9 +133,9 @@ int sample_hash_dedup(const uint32_t *indptr, const uint32_t *indices, const flo
     }
   }
 #define FGNN_HD(MODE)                                                                                              \
-  hipLaunchKernelGGL(hash_dedup_kernel, dim3(nb), dim3(kBlock), lds, st, indptr, indices, prob_table, alias_table, \
-                     input, num_input, d_num_input, cap, F, out_src, out_dst, src_mode, seed, batch_key, tag, scan, \
-                     d_num_out, MODE, sums)
+  hipLaunchKernelGGL(hash_dedup_kernel, dim3(nb), dim3(kBlock), lds, st, c.indptr, c.indices, prob_table,      \
+                     alias_table, c.input, c.num_input, c.d_num_input, cap, F, c.out_src, c.out_dst, c.src_mode,   \
+                     c.seed, c.batch_key, pro.tag, scan, c.d_num_out, MODE, sums)
   if (mode == 0) {
     FGNN_HD(0);
     if (scan_host && scan.ticket && scan.desc == scan_host->ws.desc) {
@@ -152,7 +147,7 @@ int sample_hash_dedup(const uint32_t *indptr, const uint32_t *indices, const flo
     }
   } else {
     FGNN_HD(1);
-    if (launch_scan_block_sums(sums, nb, d_num_out, nullptr, nullptr, nullptr, st) != FGNN_OK) return FGNN_EHIP;
+    if (launch_scan_block_sums(sums, nb, c.d_num_out, nullptr, nullptr, nullptr, st) != FGNN_OK) return FGNN_EHIP;
     FGNN_HD(2);
   }
 #undef FGNN_HD
@@ -172,7 +167,9 @@ extern "C" int fgnn_sample_weighted_khop_hash_dedup(const uint32_t *indptr, cons
                                                     uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out,
                                                     int src_mode, uint64_t seed, uint64_t batch_key, uint32_t layer,
                                                     void *ws, size_t ws_bytes, void *stream) {
-  return fgnn::sample_hash_dedup(indptr, indices, prob_table, alias_table, input, num_input, d_num_input,
-                                 num_input_cap, fanout, out_src, out_dst, d_num_out, src_mode, seed, batch_key, layer,
-                                 ws, ws_bytes, stream, nullptr);
+  return fgnn::sample_hash_dedup(
+      fgnn::LayerCall{indptr, const_cast<uint32_t *>(indices), input, num_input, d_num_input, num_input_cap, fanout,
+                      out_src, out_dst, d_num_out, src_mode, seed, batch_key, layer, ws, ws_bytes,
+                      static_cast<hipStream_t>(stream)},
+      prob_table, alias_table, nullptr);
 }

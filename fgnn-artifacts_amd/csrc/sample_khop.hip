@@ -478,20 +478,17 @@ __global__ __launch_bounds__(T) void khop_sample_kernel(const uint32_t *__restri
 }
 
 template <bool KHOP2>
-int launch_khop(const uint32_t *indptr, uint32_t *indices, const uint32_t *input, size_t num_input,
-                const uint32_t *d_num_input, size_t cap, size_t fanout, uint32_t *out_src, uint32_t *out_dst,
-                size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws,
-                size_t ws_bytes, hipStream_t stream, fgnn_hashtable *fuse_ht = nullptr,
-                ScanWsHost *scan_host = nullptr, const BatchStart *start = nullptr, bool resolve = false) {
-  if (fanout == 0 || fanout > 0x7fffffffu) return FGNN_EINVAL;
-  if (!d_num_input) cap = num_input;
-  if (cap == 0) {
-    if (d_num_out) FGNN_HIP_CHECK(hipMemsetAsync(d_num_out, 0, sizeof(size_t), stream));
-    return FGNN_OK;
-  }
+int launch_khop(const LayerCall &c, fgnn_hashtable *fuse_ht, const BatchStart *start, bool resolve,
+                ScanWsHost *scan_host) {
+  if (c.fanout == 0 || c.fanout > 0x7fffffffu) return FGNN_EINVAL;
+  const LayerPrologue pro = layer_prologue(c, KHOP2 ? FGNN_KHOP2 : FGNN_KHOP0);
+  if (pro.empty) return pro.rc;
+  const size_t cap = pro.cap, fanout = c.fanout, ws_bytes = c.ws_bytes;
   if (cap > 0xffffffffull) return FGNN_EINVAL;
   const uint32_t F = (uint32_t)fanout;
-  const uint32_t tag = ((KHOP2 ? FGNN_KHOP2 : FGNN_KHOP0) << 8) | (layer & 0xffu);
+  const uint32_t tag = pro.tag;
+  void *const ws = c.ws;
+  const hipStream_t stream = c.stream;
   const size_t words_per_seed = (KHOP2 ? 3u : 1u) * (size_t)F;
   // seeds per workgroup: as many as fit in ~120 KiB of LDS (160 KiB per CU on gfx950)
   // small workgroups for small frontiers: the kernel is latency-bound, more resident waves hide more of it
@@ -544,10 +541,10 @@ int launch_khop(const uint32_t *indptr, uint32_t *indices, const uint32_t *input
         hub.win = hub.list + 3 * hubs;
         hub.cap_hubs = (uint32_t)hubs;
         FGNN_HIP_CHECK(hipMemsetAsync(hub.count, 0, sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(khop0_hub_scan_kernel, dim3(div_up(cap, (size_t)256)), dim3(256), 0, stream, indptr, input,
-                           num_input, d_num_input, cap, F, hub);
-        hipLaunchKernelGGL(khop0_hub_kernel, dim3((unsigned)device_cu_count() * 4), dim3(256), 0, stream, hub, F, seed,
-                           batch_key, tag);
+        hipLaunchKernelGGL(khop0_hub_scan_kernel, dim3(div_up(cap, (size_t)256)), dim3(256), 0, stream, c.indptr, c.input,
+                           c.num_input, c.d_num_input, cap, F, hub);
+        hipLaunchKernelGGL(khop0_hub_kernel, dim3((unsigned)device_cu_count() * 4), dim3(256), 0, stream, hub, F, c.seed,
+                           c.batch_key, tag);
       }
     }
   }
@@ -562,21 +559,21 @@ int launch_khop(const uint32_t *indptr, uint32_t *indices, const uint32_t *input
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));             \
       attr_done = true;                                                                                        \
     }                                                                                                          \
-    /* single pass (no count kernel, no scan kernel) for grids of up to 1536 workgroups (every tile sums all its    */ \
-    /* predecessors' aggregates: O(tiles^2) descriptor reads); a waiter that outlasts its poll budget recomputes    */ \
-    /* the missing aggregates itself, so residency and dispatch order are not assumed                              */ \
-    if (want_scan && nb <= 1536) scan = scan_host->next(0, nb);                                            \
+    /* single pass (no count kernel, no scan kernel) for grids of up to kSinglePassMaxTiles workgroups (every  */ \
+    /* tile sums all its predecessors' aggregates: O(tiles^2) descriptor reads); a waiter that outlasts its    */ \
+    /* poll budget recomputes the missing aggregates itself, so residency and dispatch order are not assumed   */ \
+    if (want_scan && nb <= kSinglePassMaxTiles) scan = scan_host->next(0, nb);                                 \
     if (!scan.desc) {                                                                                          \
       scan.log = phase_log_base();                                                                             \
-      hipLaunchKernelGGL((khop_count_kernel_s<SS>), dim3(nb), dim3(SS), 0, stream, indptr, input, num_input,   \
-                         d_num_input, cap, F, sums);                                                           \
-      if (launch_scan_block_sums(sums, nb, d_num_out, nullptr, nullptr, nullptr, stream, d_num_input, SS) !=   \
+      hipLaunchKernelGGL((khop_count_kernel_s<SS>), dim3(nb), dim3(SS), 0, stream, c.indptr, c.input,          \
+                         c.num_input, c.d_num_input, cap, F, sums);                                            \
+      if (launch_scan_block_sums(sums, nb, c.d_num_out, nullptr, nullptr, nullptr, stream, c.d_num_input, SS) != \
           FGNN_OK)                                                                                             \
         return FGNN_EHIP;                                                                                      \
     }                                                                                                          \
-    hipLaunchKernelGGL((khop_sample_kernel<SS, 256, KHOP2, FM>), dim3(nb), dim3(256), lds, stream, indptr, indices, \
-                       input, num_input, d_num_input, cap, F, sums, out_src, out_dst, src_mode, seed,          \
-                       batch_key, tag, fuse, scan, d_num_out, hub FGNN_ABLATE_ARG(ablate));                    \
+    hipLaunchKernelGGL((khop_sample_kernel<SS, 256, KHOP2, FM>), dim3(nb), dim3(256), lds, stream, c.indptr,        \
+                       c.indices, c.input, c.num_input, c.d_num_input, cap, F, sums, c.out_src, c.out_dst,     \
+                       c.src_mode, c.seed, c.batch_key, tag, fuse, scan, c.d_num_out, hub FGNN_ABLATE_ARG(ablate)); \
   } while (0)
 #define FGNN_LAUNCH_KHOP(SS)                                                                                   \
   do {                                                                                                         \
@@ -597,32 +594,11 @@ int launch_khop(const uint32_t *indptr, uint32_t *indices, const uint32_t *input
 
 }  // namespace
 
-int sample_khop_fused(bool khop2, const uint32_t *indptr, uint32_t *indices, const uint32_t *input, size_t num_input,
-                      const uint32_t *d_num_input, size_t cap, size_t fanout, uint32_t *out_src, uint32_t *out_dst,
-                      size_t *d_num_out, uint64_t seed, uint64_t batch_key, uint32_t layer, fgnn_hashtable *ht,
-                      void *ws, size_t ws_bytes, void *stream, ScanWsHost *scan, const BatchStart *start, bool resolve) {
-  if (!ht) return FGNN_EINVAL;
-  if (start && (d_num_input || !start->n2o)) return FGNN_EINVAL;  // the first launch takes the seeds with a host count
-  auto st = static_cast<hipStream_t>(stream);
-  return khop2 ? launch_khop<true>(indptr, indices, input, num_input, d_num_input, cap, fanout, out_src, out_dst,
-                                   d_num_out, FGNN_SRC_LOCAL, seed, batch_key, layer, ws, ws_bytes, st, ht, scan, start,
-                                   resolve)
-               : launch_khop<false>(indptr, indices, input, num_input, d_num_input, cap, fanout, out_src, out_dst,
-                                    d_num_out, FGNN_SRC_LOCAL, seed, batch_key, layer, ws, ws_bytes, st, ht, scan, start,
-                                    resolve);
-}
-
-// the same sampler without the fused insert, but with the slot's look-back descriptors (one launch): the engine's
-// split last layer -- khop2's CSR-order chain then ends with this kernel, the dedup insert runs behind it
-int sample_khop_plain(bool khop2, const uint32_t *indptr, uint32_t *indices, const uint32_t *input, size_t num_input,
-                      const uint32_t *d_num_input, size_t cap, size_t fanout, uint32_t *out_src, uint32_t *out_dst,
-                      size_t *d_num_out, uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes,
-                      void *stream, ScanWsHost *scan) {
-  auto st = static_cast<hipStream_t>(stream);
-  return khop2 ? launch_khop<true>(indptr, indices, input, num_input, d_num_input, cap, fanout, out_src, out_dst,
-                                   d_num_out, FGNN_SRC_LOCAL, seed, batch_key, layer, ws, ws_bytes, st, nullptr, scan)
-               : launch_khop<false>(indptr, indices, input, num_input, d_num_input, cap, fanout, out_src, out_dst,
-                                    d_num_out, FGNN_SRC_LOCAL, seed, batch_key, layer, ws, ws_bytes, st, nullptr, scan);
+int sample_khop(const LayerCall &c, bool khop2, fgnn_hashtable *ht, const BatchStart *start, bool resolve,
+                ScanWsHost *scan) {
+  if (!ht && (start || resolve)) return FGNN_EINVAL;
+  if (start && (c.d_num_input || !start->n2o)) return FGNN_EINVAL;  // the first launch takes the seeds with a host count
+  return khop2 ? launch_khop<true>(c, ht, start, resolve, scan) : launch_khop<false>(c, ht, start, resolve, scan);
 }
 
 }  // namespace fgnn
@@ -631,16 +607,18 @@ extern "C" int fgnn_sample_khop0(const uint32_t *indptr, const uint32_t *indices
                                  size_t num_input, const uint32_t *d_num_input, size_t num_input_cap, size_t fanout,
                                  uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out, int src_mode, uint64_t seed,
                                  uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes, void *stream) {
-  return fgnn::launch_khop<false>(indptr, const_cast<uint32_t *>(indices), input, num_input, d_num_input,
-                                  num_input_cap, fanout, out_src, out_dst, d_num_out, src_mode, seed, batch_key, layer,
-                                  ws, ws_bytes, static_cast<hipStream_t>(stream));
+  return fgnn::sample_khop(fgnn::LayerCall{indptr, const_cast<uint32_t *>(indices), input, num_input, d_num_input,
+                                           num_input_cap, fanout, out_src, out_dst, d_num_out, src_mode, seed,
+                                           batch_key, layer, ws, ws_bytes, static_cast<hipStream_t>(stream)},
+                           /*khop2=*/false);
 }
 
 extern "C" int fgnn_sample_khop2(const uint32_t *indptr, uint32_t *indices, const uint32_t *input, size_t num_input,
                                  const uint32_t *d_num_input, size_t num_input_cap, size_t fanout, uint32_t *out_src,
                                  uint32_t *out_dst, size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key,
                                  uint32_t layer, void *ws, size_t ws_bytes, void *stream) {
-  return fgnn::launch_khop<true>(indptr, indices, input, num_input, d_num_input, num_input_cap, fanout, out_src,
-                                 out_dst, d_num_out, src_mode, seed, batch_key, layer, ws, ws_bytes,
-                                 static_cast<hipStream_t>(stream));
+  return fgnn::sample_khop(fgnn::LayerCall{indptr, indices, input, num_input, d_num_input, num_input_cap, fanout,
+                                           out_src, out_dst, d_num_out, src_mode, seed, batch_key, layer, ws, ws_bytes,
+                                           static_cast<hipStream_t>(stream)},
+                           /*khop2=*/true);
 }

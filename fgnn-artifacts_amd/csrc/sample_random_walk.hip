@@ -234,30 +234,26 @@ extern "C" int fgnn_sample_random_walk(const uint32_t *indptr, const uint32_t *i
                                        uint32_t *out_src, uint32_t *out_dst, uint32_t *out_data, size_t *d_num_out,
                                        int src_mode, uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws,
                                        size_t ws_bytes, void *stream) {
-  return fgnn::sample_random_walk_ex(indptr, indices, input, num_input, d_num_input, num_input_cap, walk_len,
-                                     restart_prob, num_walks, K, out_src, out_dst, out_data, d_num_out, src_mode, seed,
-                                     batch_key, layer, ws, ws_bytes, stream, nullptr);
+  return fgnn::sample_random_walk(
+      LayerCall{indptr, const_cast<uint32_t *>(indices), input, num_input, d_num_input, num_input_cap, K, out_src,
+                out_dst, d_num_out, src_mode, seed, batch_key, layer, ws, ws_bytes, static_cast<hipStream_t>(stream)},
+      walk_len, restart_prob, num_walks, out_data, nullptr);
 }
 
-int fgnn::sample_random_walk_ex(const uint32_t *indptr, const uint32_t *indices, const uint32_t *input, size_t num_input,
-                                const uint32_t *d_num_input, size_t num_input_cap, size_t walk_len, double restart_prob,
-                                size_t num_walks, size_t K, uint32_t *out_src, uint32_t *out_dst, uint32_t *out_data,
-                                size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key, uint32_t layer,
-                                void *ws, size_t ws_bytes, void *stream, ScanWsHost *scan) {
-  auto st = static_cast<hipStream_t>(stream);
-  size_t cap = d_num_input ? num_input_cap : num_input;
+int fgnn::sample_random_walk(const LayerCall &c, size_t walk_len, double restart_prob, size_t num_walks,
+                             uint32_t *out_data, ScanWsHost *scan) {
+  const size_t K = c.fanout;
   if (walk_len == 0 || num_walks == 0 || K == 0) return FGNN_EINVAL;
   const size_t P = walk_len * num_walks;
   if (P > 4096 || K > 0xffff) return FGNN_EINVAL;  // seeds per workgroup * 2P words of LDS (<= 128 KiB)
-  if (cap == 0) {
-    if (d_num_out) FGNN_HIP_CHECK(hipMemsetAsync(d_num_out, 0, sizeof(size_t), st));
-    return FGNN_OK;
-  }
-  if (!indptr || !indices || !input || !out_src || !out_dst || !out_data || cap * K >= 0x7fffffffull)
+  const LayerPrologue pro = layer_prologue(c, FGNN_RANDOM_WALK);
+  if (pro.empty) return pro.rc;
+  const size_t cap = pro.cap;
+  if (!c.indptr || !c.indices || !c.input || !c.out_src || !c.out_dst || !out_data || cap * K >= 0x7fffffffull)
     return FGNN_EINVAL;
-  if (ws_bytes < fgnn_random_walk_scratch_bytes(cap, K)) return FGNN_ENOSPC;
-  const uint32_t tag = ((uint32_t)FGNN_RANDOM_WALK << 8) | (layer & 0xffu);
-  uint32_t *pad_dst = static_cast<uint32_t *>(ws);
+  if (c.ws_bytes < fgnn_random_walk_scratch_bytes(cap, K)) return FGNN_ENOSPC;
+  const hipStream_t st = c.stream;
+  uint32_t *pad_dst = static_cast<uint32_t *>(c.ws);
   uint32_t *pad_cnt = pad_dst + cap * K;
   uint32_t *seed_cnt = pad_cnt + cap * K;
   uint32_t *sums = seed_cnt + cap;
@@ -272,17 +268,16 @@ int fgnn::sample_random_walk_ex(const uint32_t *indptr, const uint32_t *indices,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     attr_done = true;
   }
-  hipLaunchKernelGGL(random_walk_topk_kernel, dim3(div_up(cap, seeds_per_wg)), dim3(kRwWaves * kWave), lds, st, indptr,
-                     indices, input, num_input, d_num_input, cap, (uint32_t)walk_len, restart_prob, (uint32_t)num_walks,
-                     (uint32_t)K, W, pad_dst, pad_cnt, seed_cnt, seed, batch_key, tag);
+  hipLaunchKernelGGL(random_walk_topk_kernel, dim3(div_up(cap, seeds_per_wg)), dim3(kRwWaves * kWave), lds, st, c.indptr,
+                     c.indices, c.input, c.num_input, c.d_num_input, cap, (uint32_t)walk_len, restart_prob,
+                     (uint32_t)num_walks, (uint32_t)K, W, pad_dst, pad_cnt, seed_cnt, c.seed, c.batch_key, pro.tag);
   if (scan) {  // batch driver: counts -> offsets -> compacted COO in one launch
-    constexpr size_t kSinglePassTiles = 1536;
-    const int ipt = nb <= kSinglePassTiles ? 1 : nb <= 4 * kSinglePassTiles ? 4 : nb <= 16 * kSinglePassTiles ? 16 : 0;
+    const int ipt = single_pass_items_per_thread(nb);
     const size_t grid = ipt ? div_up(cap, (size_t)kBlock * ipt) : 0;
     if (ipt && grid <= scan->ws.max_tiles) {
 #define FGNN_RW_EMIT(I)                                                                                              \
-  hipLaunchKernelGGL((rw_emit_sp_kernel<I>), dim3(grid), dim3(kBlock), 0, st, input, seed_cnt, cap, (uint32_t)K, pad_dst, \
-                     pad_cnt, out_src, out_dst, out_data, src_mode, scan->next(0, grid), d_num_out)
+  hipLaunchKernelGGL((rw_emit_sp_kernel<I>), dim3(grid), dim3(kBlock), 0, st, c.input, seed_cnt, cap, (uint32_t)K, pad_dst, \
+                     pad_cnt, c.out_src, c.out_dst, out_data, c.src_mode, scan->next(0, grid), c.d_num_out)
       if (ipt == 1) FGNN_RW_EMIT(1);
       else if (ipt == 4) FGNN_RW_EMIT(4);
       else FGNN_RW_EMIT(16);
@@ -291,8 +286,8 @@ int fgnn::sample_random_walk_ex(const uint32_t *indptr, const uint32_t *indices,
     }
   }
   hipLaunchKernelGGL(rw_sums_kernel, dim3(nb), dim3(kBlock), 0, st, seed_cnt, cap, sums);
-  if (launch_scan_block_sums(sums, nb, d_num_out, nullptr, nullptr, nullptr, st) != FGNN_OK) return FGNN_EHIP;
-  hipLaunchKernelGGL(rw_emit_kernel, dim3(nb), dim3(kBlock), 0, st, input, seed_cnt, cap, (uint32_t)K, pad_dst, pad_cnt,
-                     sums, out_src, out_dst, out_data, src_mode);
+  if (launch_scan_block_sums(sums, nb, c.d_num_out, nullptr, nullptr, nullptr, st) != FGNN_OK) return FGNN_EHIP;
+  hipLaunchKernelGGL(rw_emit_kernel, dim3(nb), dim3(kBlock), 0, st, c.input, seed_cnt, cap, (uint32_t)K, pad_dst,
+                     pad_cnt, sums, c.out_src, c.out_dst, out_data, c.src_mode);
   return launch_status(__func__);
 }

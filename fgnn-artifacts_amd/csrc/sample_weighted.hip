@@ -250,8 +250,6 @@ __global__ __launch_bounds__(kBlock) void weighted_emit_kernel(const uint32_t *_
 constexpr int kWordsPerThread = 16;
 constexpr int kWordsPerBlock = kBlock * kWordsPerThread;  // bitmap words one workgroup of the popcount passes covers
 
-constexpr size_t kSinglePassTiles = 1536;  // grids whose workgroups sum all their predecessors' aggregates (fgnn_device.h)
-
 // back to all zero (only where the single-pass emit kernel, which does this on the way, cannot be used)
 __global__ __launch_bounds__(kBlock) void rank_clear_kernel(const uint32_t *__restrict__ keys, size_t cap,
                                                             uint32_t *bitmap) {
@@ -468,32 +466,25 @@ extern "C" size_t fgnn_weighted_scratch_bytes(size_t num_input_cap, size_t fanou
              sizeof(uint32_t) + 256;
 }
 
-namespace fgnn {
-namespace {
-
-int launch_with_replacement(int mode, int sample_type, const uint32_t *indptr, const uint32_t *indices,
-                            const float *table_f, const uint32_t *alias, const uint32_t *input, size_t num_input,
-                            const uint32_t *d_num_input, size_t num_input_cap, size_t fanout, uint32_t *out_src,
-                            uint32_t *out_dst, size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key,
-                            uint32_t layer, void *ws, size_t ws_bytes, void *stream, size_t num_node = 0,
-                            const RankWs *rank = nullptr, PrefixTreeView tree = PrefixTreeView{nullptr, nullptr, nullptr}) {
+int fgnn::sample_with_replacement(const LayerCall &c, int sample_type, const float *table_f, const uint32_t *alias,
+                                  size_t num_node, const RankWs *rank, PrefixTreeView tree) {
   // rank != null: the caller guarantees unique seeds below num_node (the batch driver's frontier) and owns an all-zero
   // bitmap over the id space: the seeds are ordered by counting bits, nothing is sorted and no library is called
-  auto st = static_cast<hipStream_t>(stream);
-  size_t cap = d_num_input ? num_input_cap : num_input;
-  if (fanout == 0 || fanout > 0xffffu) return FGNN_EINVAL;
-  if (cap == 0) {
-    if (d_num_out) FGNN_HIP_CHECK(hipMemsetAsync(d_num_out, 0, sizeof(size_t), st));
-    return FGNN_OK;
-  }
-  if (!indptr || !indices || !input || cap * fanout >= 0x7fffffffull) return FGNN_EINVAL;
+  const int mode = sample_type == FGNN_KHOP1 ? 1 : sample_type == FGNN_WEIGHTED_KHOP ? 2 : 0;
+  if (mode != 0) tree = PrefixTreeView{nullptr, nullptr, nullptr};
+  if (c.fanout == 0 || c.fanout > 0xffffu) return FGNN_EINVAL;
+  const LayerPrologue pro = layer_prologue(c, sample_type);
+  if (pro.empty) return pro.rc;
+  const size_t cap = pro.cap;
+  if (!c.indptr || !c.indices || !c.input || cap * c.fanout >= 0x7fffffffull) return FGNN_EINVAL;
   if ((mode != 1 && !table_f) || (mode == 2 && !alias)) return FGNN_EINVAL;
-  if (ws_bytes < fgnn_weighted_scratch_bytes(cap, fanout)) return FGNN_ENOSPC;
+  if (c.ws_bytes < fgnn_weighted_scratch_bytes(cap, c.fanout)) return FGNN_ENOSPC;
   if (rank && (!rank->bitmap || !rank->scan || num_node == 0)) return FGNN_EINVAL;
-  const uint32_t F = (uint32_t)fanout;
-  const uint32_t tag = ((uint32_t)sample_type << 8) | (layer & 0xffu);
+  const uint32_t F = (uint32_t)c.fanout;
+  const uint32_t tag = pro.tag;
+  const hipStream_t st = c.stream;
   const size_t nb = div_up(cap, kBlock);
-  uint32_t *tmp_dst = static_cast<uint32_t *>(ws);
+  uint32_t *tmp_dst = static_cast<uint32_t *>(c.ws);
   uint32_t *keys = tmp_dst + cap * F;
   uint32_t *vals = keys + cap;
   uint32_t *keys_out = vals + cap;
@@ -509,9 +500,9 @@ int launch_with_replacement(int mode, int sample_type, const uint32_t *indptr, c
     size_t blocks = div_up(cap, seeds_per_wg);
     if (blocks > 256 * 32) blocks = 256 * 32;
 #define FGNN_DRAWC(M)                                                                                            \
-  hipLaunchKernelGGL((weighted_draw_count_kernel<M>), dim3(blocks), dim3(kBlock), 0, st, indptr, indices, table_f, \
-                     alias, input, num_input, d_num_input, cap, F, tmp_dst, keys, vals, cnt, bitmap, order, seed,    \
-                     batch_key, tag, tree)
+  hipLaunchKernelGGL((weighted_draw_count_kernel<M>), dim3(blocks), dim3(kBlock), 0, st, c.indptr, c.indices,     \
+                     table_f, alias, c.input, c.num_input, c.d_num_input, cap, F, tmp_dst, keys, vals, cnt, bitmap, \
+                     order, c.seed, c.batch_key, tag, tree)
     if (mode == 1) FGNN_DRAWC(1);
     else if (mode == 2) FGNN_DRAWC(2);
     else FGNN_DRAWC(0);
@@ -520,21 +511,21 @@ int launch_with_replacement(int mode, int sample_type, const uint32_t *indptr, c
     size_t blocks = div_up(cap * F, kBlock);
     if (blocks > 256 * 32) blocks = 256 * 32;
 #define FGNN_DRAW(M)                                                                                              \
-  hipLaunchKernelGGL((weighted_draw_kernel<M>), dim3(blocks), dim3(kBlock), 0, st, indptr, indices, table_f, alias, \
-                     input, num_input, d_num_input, cap, F, tmp_dst, seed, batch_key, tag, tree)
+  hipLaunchKernelGGL((weighted_draw_kernel<M>), dim3(blocks), dim3(kBlock), 0, st, c.indptr, c.indices, table_f,    \
+                     alias, c.input, c.num_input, c.d_num_input, cap, F, tmp_dst, c.seed, c.batch_key, tag, tree)
     if (mode == 1) FGNN_DRAW(1);
     else if (mode == 2) FGNN_DRAW(2);
     else FGNN_DRAW(0);
 #undef FGNN_DRAW
-    hipLaunchKernelGGL(weighted_count_kernel, dim3(nb), dim3(kBlock), 0, st, indptr, input, num_input, d_num_input, cap,
-                       F, tmp_dst, keys, vals, cnt, bitmap, order);
+    hipLaunchKernelGGL(weighted_count_kernel, dim3(nb), dim3(kBlock), 0, st, c.indptr, c.input, c.num_input,
+                       c.d_num_input, cap, F, tmp_dst, keys, vals, cnt, bitmap, order);
   }
   if (rank) {
     // order by counting bits below each seed id (see the file header): 5 launches per layer in all
     const size_t words = rank_words(num_node);
     const size_t nb2 = div_up(words, (size_t)kWordsPerBlock);
     uint32_t *pre = bitmap + words;
-    if (nb2 <= kSinglePassTiles && nb2 <= rank->scan->ws.max_tiles) {
+    if (nb2 <= kSinglePassMaxTiles && nb2 <= rank->scan->ws.max_tiles) {
       hipLaunchKernelGGL(rank_prefix_kernel, dim3(nb2), dim3(kBlock), 0, st, bitmap, words, pre,
                          rank->scan->next(0, nb2));
     } else {  // graphs beyond ~200 M nodes: per-workgroup sums -> scan -> prefixes
@@ -547,12 +538,12 @@ int launch_with_replacement(int mode, int sample_type, const uint32_t *indptr, c
       hipLaunchKernelGGL((rank_popcount_kernel<1>), dim3(nb2), dim3(kBlock), 0, st, bitmap, words, sums2, pre);
     }
     hipLaunchKernelGGL(rank_scatter_kernel, dim3(nb), dim3(kBlock), 0, st, keys, cap, bitmap, pre, order);
-    const int ipt = nb <= kSinglePassTiles ? 1 : nb <= 4 * kSinglePassTiles ? 4 : nb <= 16 * kSinglePassTiles ? 16 : 0;
+    const int ipt = single_pass_items_per_thread(nb);
     const size_t grid = ipt ? div_up(cap, (size_t)kBlock * ipt) : 0;
     if (ipt && grid <= rank->scan->ws.max_tiles) {
 #define FGNN_EMIT(I)                                                                                                  \
-  hipLaunchKernelGGL((weighted_emit_sp_kernel<I>), dim3(grid), dim3(kBlock), 0, st, input, order, cnt, keys, cap, F, \
-                     tmp_dst, out_src, out_dst, src_mode, rank->scan->next(0, grid), d_num_out, bitmap)
+  hipLaunchKernelGGL((weighted_emit_sp_kernel<I>), dim3(grid), dim3(kBlock), 0, st, c.input, order, cnt, keys, cap, \
+                     F, tmp_dst, c.out_src, c.out_dst, c.src_mode, rank->scan->next(0, grid), c.d_num_out, bitmap)
       if (ipt == 1) FGNN_EMIT(1);
       else if (ipt == 4) FGNN_EMIT(4);
       else FGNN_EMIT(16);
@@ -568,26 +559,12 @@ int launch_with_replacement(int mode, int sample_type, const uint32_t *indptr, c
     if (launch_sort_pairs_u32(keys, keys_out, vals, order, cap, sort_ws, st, nullptr, &order) != FGNN_OK) return FGNN_EHIP;
   }
   hipLaunchKernelGGL(weighted_sorted_sums_kernel, dim3(nb), dim3(kBlock), 0, st, order, cnt, cap, sums);
-  if (launch_scan_block_sums(sums, nb, d_num_out, nullptr, nullptr, nullptr, st) != FGNN_OK) return FGNN_EHIP;
-  hipLaunchKernelGGL(weighted_emit_kernel, dim3(nb), dim3(kBlock), 0, st, input, order, cnt, cap, F, tmp_dst, sums,
-                     out_src, out_dst, src_mode);
+  if (launch_scan_block_sums(sums, nb, c.d_num_out, nullptr, nullptr, nullptr, st) != FGNN_OK) return FGNN_EHIP;
+  hipLaunchKernelGGL(weighted_emit_kernel, dim3(nb), dim3(kBlock), 0, st, c.input, order, cnt, cap, F, tmp_dst,
+                     sums, c.out_src, c.out_dst, c.src_mode);
   return launch_status(__func__);
 }
 
-}  // namespace
-}  // namespace fgnn
-
-int fgnn::sample_with_replacement_ex(int sample_type, const uint32_t *indptr, const uint32_t *indices,
-                                     const float *table_f, const uint32_t *alias, const uint32_t *input,
-                                     size_t num_input, const uint32_t *d_num_input, size_t num_input_cap, size_t fanout,
-                                     uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out, int src_mode,
-                                     uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes,
-                                     void *stream, size_t num_node, const RankWs *rank, PrefixTreeView tree) {
-  const int mode = sample_type == FGNN_KHOP1 ? 1 : sample_type == FGNN_WEIGHTED_KHOP ? 2 : 0;
-  return launch_with_replacement(mode, sample_type, indptr, indices, table_f, alias, input, num_input, d_num_input,
-                                 num_input_cap, fanout, out_src, out_dst, d_num_out, src_mode, seed, batch_key, layer,
-                                 ws, ws_bytes, stream, num_node, rank, mode == 0 ? tree : PrefixTreeView{nullptr, nullptr, nullptr});
-}
 
 extern "C" int fgnn_sample_weighted_khop_prefix(const uint32_t *indptr, const uint32_t *indices, const float *prefix,
                                                 const uint32_t *input, size_t num_input,
@@ -595,18 +572,20 @@ extern "C" int fgnn_sample_weighted_khop_prefix(const uint32_t *indptr, const ui
                                                 uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out, int src_mode,
                                                 uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws,
                                                 size_t ws_bytes, void *stream) {
-  return fgnn::launch_with_replacement(0, FGNN_WEIGHTED_KHOP_PREFIX, indptr, indices, prefix, nullptr, input, num_input,
-                                       d_num_input, num_input_cap, fanout, out_src, out_dst, d_num_out, src_mode, seed,
-                                       batch_key, layer, ws, ws_bytes, stream);
+  return fgnn::sample_with_replacement(
+      LayerCall{indptr, const_cast<uint32_t *>(indices), input, num_input, d_num_input, num_input_cap, fanout, out_src,
+                out_dst, d_num_out, src_mode, seed, batch_key, layer, ws, ws_bytes, static_cast<hipStream_t>(stream)},
+      FGNN_WEIGHTED_KHOP_PREFIX, prefix, nullptr);
 }
 
 extern "C" int fgnn_sample_khop1(const uint32_t *indptr, const uint32_t *indices, const uint32_t *input,
                                  size_t num_input, const uint32_t *d_num_input, size_t num_input_cap, size_t fanout,
                                  uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out, int src_mode, uint64_t seed,
                                  uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes, void *stream) {
-  return fgnn::launch_with_replacement(1, FGNN_KHOP1, indptr, indices, nullptr, nullptr, input, num_input, d_num_input,
-                                       num_input_cap, fanout, out_src, out_dst, d_num_out, src_mode, seed, batch_key,
-                                       layer, ws, ws_bytes, stream);
+  return fgnn::sample_with_replacement(
+      LayerCall{indptr, const_cast<uint32_t *>(indices), input, num_input, d_num_input, num_input_cap, fanout, out_src,
+                out_dst, d_num_out, src_mode, seed, batch_key, layer, ws, ws_bytes, static_cast<hipStream_t>(stream)},
+      FGNN_KHOP1, nullptr, nullptr);
 }
 
 extern "C" int fgnn_sample_weighted_khop(const uint32_t *indptr, const uint32_t *indices, const float *prob_table,
@@ -615,7 +594,8 @@ extern "C" int fgnn_sample_weighted_khop(const uint32_t *indptr, const uint32_t 
                                          uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out, int src_mode,
                                          uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes,
                                          void *stream) {
-  return fgnn::launch_with_replacement(2, FGNN_WEIGHTED_KHOP, indptr, indices, prob_table, alias_table, input,
-                                       num_input, d_num_input, num_input_cap, fanout, out_src, out_dst, d_num_out,
-                                       src_mode, seed, batch_key, layer, ws, ws_bytes, stream);
+  return fgnn::sample_with_replacement(
+      LayerCall{indptr, const_cast<uint32_t *>(indices), input, num_input, d_num_input, num_input_cap, fanout, out_src,
+                out_dst, d_num_out, src_mode, seed, batch_key, layer, ws, ws_bytes, static_cast<hipStream_t>(stream)},
+      FGNN_WEIGHTED_KHOP, prob_table, alias_table);
 }
