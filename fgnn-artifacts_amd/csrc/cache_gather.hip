@@ -234,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void gather_rows16_kernel(chunk16 *__restri
   if (tail.meta_dst && blockIdx.x == gridDim.x - 1 && threadIdx.x < tail.meta_words)
     tail.meta_dst[threadIdx.x] = tail.meta_src[threadIdx.x];
   const uint32_t n = (uint32_t)resolve_count(n_host, d_n, cap);
-  const uint32_t total = n * cpr;  // host guarantees cap * cpr < 2^32
+  const uint32_t total = n * cpr;  // the host admits a launch only if cap * cpr + grid * tile <= 2^32 (walk_fits)
   constexpr uint32_t tile = kBlock * UNROLL;
   const uint32_t full = total / tile * tile;
   uint32_t tile0 = blockIdx.x * tile;
@@ -301,7 +301,7 @@ __device__ __forceinline__ void gather_band(chunk16 *__restrict__ out, const chu
                                             const uint32_t *__restrict__ dst_index, uint32_t n, uint32_t cpr_rt,
                                             uint32_t src_mask, uint32_t bid, uint32_t nb) {
   const uint32_t cpr = CPR ? (uint32_t)CPR : cpr_rt;
-  const uint32_t total = n * cpr;  // host guarantees cap * cpr < 2^32
+  const uint32_t total = n * cpr;  // the host admits a job only if cap * cpr + nb * tile <= 2^32 (walk_fits)
   constexpr uint32_t tile = kBlock * UNROLL;
   const uint32_t full = total / tile * tile;
   uint32_t tile0 = bid * tile;
@@ -416,7 +416,8 @@ __global__ __launch_bounds__(kBlock) void extract_fused_kernel(const FusedArgs a
       const uint32_t total = s_begin[ns];
       const uint32_t stride = nb * kBlock;
       constexpr int U = 8;
-      // (i0 + u * stride stays below 2^32: the host refuses copies of 2^31 words and more)
+      // (i0 + u * stride stays below 2^32: the host refuses copies of 2^31 words and more, and any whose words +
+      // nb * kBlock * U pass 2^32 -- walk_fits)
       for (uint32_t i0 = bid * kBlock + threadIdx.x; i0 < total; i0 += U * stride) {
         uint32_t v[U];
         uint32_t *d[U];
@@ -573,10 +574,116 @@ extern "C" int fgnn_gather_rows_shared(void *out, const void *src, const uint32_
                               shared_gpu ? fgnn::kSharedGpuHostGrid : 0);
 }
 
+// ---- the 32-bit walks' bound: ONE admissibility rule, owned by the host ------------------------------------------------
+// gather_rows16_kernel and gather_band walk a list's chunks with a 32-bit cursor: workgroup b starts at b * tile and adds
+// grid * tile while the cursor is below `full` (the chunk total rounded down to whole tiles); the ragged tail belongs to
+// the workgroup whose cursor ends exactly on `full`.  The last addition of a workgroup starts below `total` and lands
+// below total + grid * tile: if that passes 2^32 the cursor wraps to a small value, is below `full` again, and the
+// workgroup starts over -- it never ends (total 0xfffffc00, 1024 workgroups, tile 1024: workgroup 0 is back at tile 0
+// after 4096 steps).  So a launch is admitted only if
+//     total + grid * tile <= 2^32            total = capacity in rows * chunks per row, grid = what the launch really gets
+// and nothing else in this file compares a chunk total with 2^32.  A device-side count only shrinks `total` below the
+// capacity the rule was applied to.  What was checked by reading for the other 32-bit cursors of this file:
+//  * the link band of extract_fused_kernel is gather_band with nb = link_wgs and the link band's own tile (kBlock * UL):
+//    the same walk, the same rule, applied with those two numbers (fused_plan); the HBM band likewise with nb = its
+//    workgroups and kBlock * UH, for the miss list (no link band) and the hit list;
+//  * the label loops (`i += grid * kBlock`, i < num_label) have the cursor's shape without a tail: they wrap -- and
+//    never end -- when num_label + grid * kBlock passes 2^32.  Same rule with rows = num_label, one chunk per row and a
+//    tile of kBlock (job_ok only bounds num_label by 2^32 - 1, which is not enough by itself);
+//  * the segment copy (`i0 += U * stride`, stride = nb * kBlock) reads i = i0 + u * stride for u < U inside one step and
+//    guards each with `i >= i0`, so a wrapped i is dropped, not copied; the cursor i0 itself must not wrap either, which
+//    is the rule with rows = words, a tile of kBlock * U and the HBM band's workgroups.  The refusal of 2^31 words and
+//    more stays: with it and a band of at most a few thousand workgroups the rule cannot fail, it is applied anyway so
+//    that no walk of this file depends on an argument made elsewhere;
+//  * gather_rows_elem_kernel, cache_count / cache_split and cache_table_scatter index with size_t: no bound needed.
+namespace fgnn {
+namespace {
+
+constexpr uint64_t kWalkSpan = uint64_t(1) << 32;  // what a 32-bit cursor can tell apart
+
+// workgroups of a launch that walks `total` chunks in tiles of `tile` under a grid cap
+size_t walk_grid(size_t total, size_t tile, size_t grid_cap) { return std::min(div_up(total, tile), grid_cap); }
+
+// THE rule: may `grid` workgroups walk rows * cpr chunks in tiles of `tile` with a 32-bit cursor?
+bool walk_fits(size_t rows, size_t cpr, size_t grid, size_t tile) {
+  if (rows == 0) return true;
+  if (cpr == 0 || tile == 0 || grid == 0 || tile > kWalkSpan || cpr > kWalkSpan) return false;
+  if (rows > kWalkSpan / cpr || grid > kWalkSpan / tile) return false;
+  return rows * cpr + grid * tile <= kWalkSpan;
+}
+
+// How a gather of `rows` rows of `cpr` chunks is launched: launch k takes rows [k * rows_per, k * rows_per + count(k)) on
+// grid(k) workgroups.  One launch where the rule admits it; host-sized gathers beyond that go in slices of 2^31 chunks
+// (every slice admitted by the same rule); a device-sized count cannot be sliced (the host does not know where it
+// ends), nor can a masked gather without a source index (a slice would mask its row number relative to the slice's
+// base pointer): those are refused.
+struct GatherPlan {
+  int code = FGNN_OK;
+  size_t launches = 0, rows = 0, rows_per = 0, cpr = 0, tile = 0, grid_cap = 0;
+  size_t first_row(size_t k) const { return k * rows_per; }
+  size_t count(size_t k) const { return std::min(rows_per, rows - k * rows_per); }
+  size_t grid(size_t k) const { return walk_grid(count(k) * cpr, tile, grid_cap); }
+};
+
+GatherPlan gather_plan(size_t rows, size_t cpr, bool device_sized, bool has_src_index, uint32_t src_row_mask,
+                       size_t grid_cap, size_t tile) {
+  GatherPlan p;
+  p.rows = rows; p.cpr = cpr; p.tile = tile; p.grid_cap = grid_cap;
+  if (rows == 0) return p;
+  p.code = FGNN_EINVAL;
+  if (!walk_fits(1, cpr, 1, tile) || grid_cap == 0) return p;  // not even one row
+  if (rows <= kWalkSpan / cpr && walk_fits(rows, cpr, walk_grid(rows * cpr, tile, grid_cap), tile)) {
+    p.launches = 1;
+    p.rows_per = rows;
+    p.code = FGNN_OK;
+    return p;
+  }
+  if (device_sized || (!has_src_index && src_row_mask != 0xFFFFFFFFu)) return p;
+  p.rows_per = (size_t(1) << 31) / cpr;
+  if (p.rows_per == 0 || !walk_fits(p.rows_per, cpr, walk_grid(p.rows_per * cpr, tile, grid_cap), tile)) return p;
+  p.launches = div_up(rows, p.rows_per);
+  p.code = FGNN_OK;
+  return p;
+}
+
+constexpr size_t kGatherWgPerCu = 4;  // persistent workgroups per CU of a gather nobody sized otherwise
+constexpr int kGatherMaxUnroll = 8;   // the largest tile any build launches (the profiling build's FGNN_GATHER_UNROLL)
+
+}  // namespace
+}  // namespace fgnn
+
+extern "C" int fgnn_debug_gather_plan(size_t rows, size_t row_bytes, int device_sized, int has_src_index,
+                                      uint32_t src_row_mask, size_t cus, size_t wg_per_cu, int unroll, uint64_t *out,
+                                      size_t max_launches) {
+  if (row_bytes == 0 || row_bytes % 16 || cus == 0 || cus > (1u << 20) || wg_per_cu == 0 || wg_per_cu > 1024 ||
+      (unroll != 2 && unroll != 4 && unroll != 8))
+    return FGNN_EINVAL;
+  const GatherPlan p = fgnn::gather_plan(rows, row_bytes / 16, device_sized != 0, has_src_index != 0, src_row_mask,
+                                         cus * wg_per_cu, (size_t)kBlock * unroll);
+  if (p.code != FGNN_OK) return p.code;
+  if (p.launches > max_launches || p.launches > 0x7fffffffull) return FGNN_ENOSPC;
+  if (p.launches && !out) return FGNN_EINVAL;
+  for (size_t k = 0; k < p.launches; ++k) {
+    out[4 * k] = p.first_row(k);
+    out[4 * k + 1] = p.count(k);
+    out[4 * k + 2] = p.grid(k);
+    out[4 * k + 3] = p.tile;
+  }
+  return (int)p.launches;
+}
+
+// (asked before the launch's grid is known: the largest grid and tile a tailed gather may get, one launch, the count
+// taken as device-sized -- gather_rows_ex plans again with what the launch really gets)
 bool fgnn::gather_takes_tail(const void *out, const void *src, size_t n_cap, size_t dim, int dtype) {
   const size_t row_bytes = dim * dtype_bytes(dtype);
-  return row_bytes && row_bytes % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
-         reinterpret_cast<uintptr_t>(src) % 16 == 0 && n_cap > 0 && n_cap * (row_bytes / 16) < 0xffffffffull;
+  if (!row_bytes || row_bytes % 16 || reinterpret_cast<uintptr_t>(out) % 16 || reinterpret_cast<uintptr_t>(src) % 16 ||
+      n_cap == 0)
+    return false;
+  const size_t per_cu = (size_t)tune_int("FGNN_GATHER_WG_PER_CU", (int)kGatherWgPerCu);
+  const GatherPlan p = gather_plan(n_cap, row_bytes / 16, true, true, 0xFFFFFFFFu,
+                                   (size_t)device_cu_count() * std::max(per_cu, kGatherWgPerCu),
+                                   (size_t)kBlock * kGatherMaxUnroll);
+  return p.code == FGNN_OK && p.launches == 1;
 }
 
 // is `p` host memory the GPU reads over the host link?  Asked per launch that could be one (a registered table may be
@@ -601,26 +708,13 @@ int fgnn::gather_rows_ex(void *out, const void *src, const uint32_t *src_index, 
   if (cap == 0) return FGNN_OK;
   if (!out || !src) return FGNN_EINVAL;
   const size_t row_bytes = dim * esz;
+  const int unroll_in = tune_int("FGNN_GATHER_UNROLL", 4);
+  const int unroll = unroll_in == 8 || unroll_in == 2 ? unroll_in : 4;
+  // (a row too wide for the chunk walk by itself -- 64 GiB -- is moved by the element kernel, which indexes with size_t)
   const bool vec = (row_bytes % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) &&
-                   (reinterpret_cast<uintptr_t>(src) % 16 == 0) && row_bytes / 16 <= 0xffffffffull;
+                   (reinterpret_cast<uintptr_t>(src) % 16 == 0) && walk_fits(1, row_bytes / 16, 1, (size_t)kBlock * unroll);
   if (vec) {
     const uint32_t cpr = (uint32_t)(row_bytes / 16);
-    if (cap * cpr >= 0xffffffffull) {
-      // the kernel indexes 16-byte chunks with 32 bits (64 GiB of rows per launch): larger host-sized gathers (e.g.
-      // filling a whole-table feature cache) go in slices; device-sized ones of that size are not supported
-      if (d_n || (!src_index && src_row_mask != 0xFFFFFFFFu)) return FGNN_EINVAL;
-      const size_t rows_per = (size_t(1) << 31) / cpr;
-      for (size_t r0 = 0; r0 < n; r0 += rows_per) {
-        const size_t m = n - r0 < rows_per ? n - r0 : rows_per;
-        const int rc = fgnn_gather_rows_masked(
-            dst_index ? out : static_cast<char *>(out) + r0 * row_bytes,
-            src_index ? src : static_cast<const char *>(src) + r0 * row_bytes, src_index ? src_index + r0 : nullptr,
-            dst_index ? dst_index + r0 : nullptr, m, nullptr, m, dim, dtype, src_row_mask, stream);  // (no tail here)
-        if (rc != FGNN_OK) return rc;
-      }
-      return FGNN_OK;
-    }
-    const size_t total = cap * cpr;
     // Rows read from HOST memory (registered / pinned: miss rows) come over the host link at ~50 GB/s, and the grid of
     // such a launch is a trade: sized like an HBM gather (1024 persistent workgroups, ~1 M loads in flight) it keeps
     // the link busiest -- a GPU that only extracts (an arch5 trainer, four batches in flight) pulls 50.6 GB/s against
@@ -632,9 +726,20 @@ int fgnn::gather_rows_ex(void *out, const void *src, const uint32_t *src_index, 
     // _WG_PER_CU / _NT / _NTS -- exist in the profiling build only.)
     const size_t host_wgs = (size_t)tune_int("FGNN_GATHER_HOST_WGS", (int)host_grid);  // 0: no special case
     const bool host_src = host_wgs != 0 && pointer_is_host(src);
-    const int unroll = tune_int("FGNN_GATHER_UNROLL", 4);
-    const size_t wg_per_cu = (size_t)tune_int("FGNN_GATHER_WG_PER_CU", wg_per_cu_in ? (int)wg_per_cu_in : 4),
+    const size_t wg_per_cu =
+                     (size_t)tune_int("FGNN_GATHER_WG_PER_CU", wg_per_cu_in ? (int)wg_per_cu_in : (int)kGatherWgPerCu),
                  cus = (size_t)device_cu_count();
+    size_t grid_cap = cus * wg_per_cu;
+    if (host_src && grid_cap > host_wgs) grid_cap = host_wgs;
+    // the kernel indexes 16-byte chunks with 32 bits (64 GiB of rows per launch, less what its walk needs: walk_fits):
+    // larger host-sized gathers (e.g. filling a whole-table feature cache) go in slices; device-sized ones of that size
+    // are not supported
+    const GatherPlan plan = gather_plan(cap, cpr, d_n != nullptr, src_index != nullptr, src_row_mask, grid_cap,
+                                        (size_t)kBlock * unroll);
+    if (plan.code != FGNN_OK) return plan.code;
+    // a tail rides on ONE launch, and its label loop is a 32-bit walk of its own
+    if (tail_in && (plan.launches != 1 || !walk_fits(tail.label_out ? tail.num_label : 0, 1, plan.grid(0), kBlock)))
+      return FGNN_EINVAL;
     // non-temporal loads: gathered rows are touched once; measured 6.4 TB/s vs 4.9 TB/s with default-policy
     // loads (profiles/r01_gather_sweep.csv)
     const bool nt = tune_int("FGNN_GATHER_NT", 1) != 0;
@@ -643,15 +748,12 @@ int fgnn::gather_rows_ex(void *out, const void *src, const uint32_t *src_index, 
     const bool nts = tune_int("FGNN_GATHER_NTS", 1) != 0;
 #define FGNN_GATHER3(U, C, N)                                                                                    \
   do {                                                                                                           \
-    size_t blocks = div_up(total, (size_t)kBlock * U);                                                           \
-    if (blocks > cus * wg_per_cu) blocks = cus * wg_per_cu;                                                      \
-    if (host_src && host_wgs && blocks > host_wgs) blocks = host_wgs;                                            \
-    if (nts) hipLaunchKernelGGL((gather_rows16_kernel<U, C, N, true>), dim3(blocks), dim3(kBlock), 0, s,          \
-                       static_cast<chunk16 *>(out), static_cast<const chunk16 *>(src), src_index, dst_index, n,  \
-                       d_n, cap, cpr, src_row_mask, tail);                                                       \
-    else hipLaunchKernelGGL((gather_rows16_kernel<U, C, N, false>), dim3(blocks), dim3(kBlock), 0, s,             \
-                       static_cast<chunk16 *>(out), static_cast<const chunk16 *>(src), src_index, dst_index, n,  \
-                       d_n, cap, cpr, src_row_mask, tail);                                                       \
+    if (nts) hipLaunchKernelGGL((gather_rows16_kernel<U, C, N, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, \
+                       static_cast<chunk16 *>(o), static_cast<const chunk16 *>(sp), si, di, nk, d_n, capk, cpr,  \
+                       src_row_mask, tail);                                                                      \
+    else hipLaunchKernelGGL((gather_rows16_kernel<U, C, N, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,  \
+                       static_cast<chunk16 *>(o), static_cast<const chunk16 *>(sp), si, di, nk, d_n, capk, cpr,  \
+                       src_row_mask, tail);                                                                      \
   } while (0)
 #define FGNN_GATHER2(U, C) do { if (nt) FGNN_GATHER3(U, C, true); else FGNN_GATHER3(U, C, false); } while (0)
 #define FGNN_GATHER(U)                                  \
@@ -661,9 +763,21 @@ int fgnn::gather_rows_ex(void *out, const void *src, const uint32_t *src_index, 
     else if (cpr == 25) FGNN_GATHER2(U, 25);            \
     else FGNN_GATHER2(U, 0);                            \
   } while (0)
-    if (unroll == 8) FGNN_GATHER(8);
-    else if (unroll == 2) FGNN_GATHER(2);
-    else FGNN_GATHER(4);
+    for (size_t k = 0; k < plan.launches; ++k) {
+      // (one launch: the caller's n, d_n and capacity as they are; slices are host-sized and carry no tail)
+      const size_t r0 = plan.first_row(k), blocks = plan.grid(k);
+      const size_t nk = plan.launches == 1 ? n : plan.count(k), capk = plan.launches == 1 ? cap : plan.count(k);
+      void *o = dst_index ? out : static_cast<char *>(out) + r0 * row_bytes;
+      const void *sp = src_index ? src : static_cast<const char *>(src) + r0 * row_bytes;
+      const uint32_t *si = src_index ? src_index + r0 : nullptr, *di = dst_index ? dst_index + r0 : nullptr;
+      if (unroll == 8) FGNN_GATHER(8);
+      else if (unroll == 2) FGNN_GATHER(2);
+      else FGNN_GATHER(4);
+      if (plan.launches > 1) {
+        const int rc = launch_status(__func__);
+        if (rc != FGNN_OK) return rc;
+      }
+    }
 #undef FGNN_GATHER
 #undef FGNN_GATHER2
 #undef FGNN_GATHER3
@@ -698,7 +812,7 @@ struct FusedPlan {
 bool fused_plan(const ExtractJob &j, FusedPlan *p) {
   const size_t esz = dtype_bytes(j.dtype);
   const size_t row_bytes = j.dim * esz;
-  if (!row_bytes || row_bytes % 16 || row_bytes / 16 > 0xffffffffull) return false;
+  if (!row_bytes || row_bytes % 16) return false;
   const size_t cap_m = j.d_counts ? j.cap : j.num_miss, cap_c = j.d_counts ? j.cap : j.num_cache;
   if ((cap_m && (!j.miss_rows || !j.miss_src || !j.miss_dst)) || (cap_c && (!j.cache_rows || !j.cache_src || !j.cache_dst)))
     return false;
@@ -706,7 +820,8 @@ bool fused_plan(const ExtractJob &j, FusedPlan *p) {
   for (const void *q : {(const void *)j.out, j.miss_rows, j.cache_rows})
     if (reinterpret_cast<uintptr_t>(q) % 16) return false;
   const size_t cpr = row_bytes / 16;
-  if (cap_m * cpr >= 0xffffffffull || cap_c * cpr >= 0xffffffffull) return false;
+  // (necessary for the rule below, and keeps the products that size the bands in range)
+  if (!walk_fits(cap_m, cpr, 1, kBlock) || !walk_fits(cap_c, cpr, 1, kBlock)) return false;
   if (j.num_segs < 0 || j.num_segs > FGNN_MAX_COPY_SEGMENTS || (j.num_segs && !j.segs)) return false;
   size_t words = 0;
   for (int k = 0; k < j.num_segs; ++k) words += j.segs[k].words;
@@ -723,6 +838,12 @@ bool fused_plan(const ExtractJob &j, FusedPlan *p) {
   if (j.tail.label_out) hbm = std::max(hbm, div_up((size_t)j.tail.num_label, (size_t)kBlock));
   if (j.tail.meta_dst) hbm = std::max<size_t>(hbm, 1);
   p->hbm = std::min(hbm, cus * per_cu);
+  // every 32-bit walk of the launch under the one rule, with the band and tile it really gets (UH = 4, the copy's U = 8)
+  if (p->link ? !walk_fits(cap_m, cpr, p->link, (size_t)kBlock * p->ul) : !walk_fits(cap_m, cpr, p->hbm, (size_t)kBlock * 4))
+    return false;
+  if (!walk_fits(cap_c, cpr, p->hbm, (size_t)kBlock * 4)) return false;
+  if (!walk_fits(j.tail.label_out ? j.tail.num_label : 0, 1, p->hbm, kBlock)) return false;
+  if (!walk_fits(words, 1, p->hbm, (size_t)kBlock * 8)) return false;
   return true;
 }
 

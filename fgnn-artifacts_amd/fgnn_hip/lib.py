@@ -53,6 +53,7 @@ SIGNATURES = {
     "fgnn_debug_set_scan_help_after": (None, (_I,)),
     "fgnn_debug_set_partition_lds_limit": (None, (_I,)),
     "fgnn_debug_partition_params": (None, (_P,)),
+    "fgnn_debug_gather_plan": (_I, (_Z, _Z, _I, _I, _U32, _Z, _Z, _I, _P, _Z)),
     "fgnn_debug_sort_pairs": (_I, (_P, _P, _Z, _P)),
     "fgnn_debug_scan_block_sums": (_I, (_P, _Z, _P, _P, _P, _P, _P, _P, _U32, _P)),
     "fgnn_debug_scan_count": (_I, (_I, _P)),
@@ -306,6 +307,20 @@ def debug_partition_params():
     out = (C.c_uint32 * len(PARTITION_PARAMS))()
     load().fgnn_debug_partition_params(out)
     return dict(zip(PARTITION_PARAMS, (int(v) for v in out)))
+
+
+def debug_gather_plan(rows, row_bytes, device_sized=False, has_src_index=True, src_row_mask=0xFFFFFFFF, cus=256,
+                      wg_per_cu=4, unroll=4, max_launches=4096):
+    """fgnn_debug_gather_plan: the launches a gather of `rows` rows of row_bytes would be made of, as a list of
+    (first_row, rows, grid, tile), or None where the library refuses the gather (FGNN_EINVAL).  Needs no GPU."""
+    out = (C.c_uint64 * (4 * max(max_launches, 1)))()
+    rc = load().fgnn_debug_gather_plan(rows, row_bytes, int(device_sized), int(has_src_index), src_row_mask, cus,
+                                       wg_per_cu, unroll, out, max_launches)
+    if rc == -1:
+        return None
+    if rc < 0:
+        _check(rc, "fgnn_debug_gather_plan")
+    return [tuple(int(v) for v in out[4 * k:4 * k + 4]) for k in range(rc)]
 
 
 def debug_scan_block_sums(sums, n=None, total64=None, total32=None, accum=None, accum_out=None, items32=None,

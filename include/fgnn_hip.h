@@ -79,6 +79,16 @@ void fgnn_debug_set_partition_lds_limit(int distinct_keys);
  * pairs stay in registers, out[6] = largest bin that is tried in LDS at all, out[7] = items per histogram / scatter
  * tile.  Touches no device. */
 void fgnn_debug_partition_params(uint32_t out[8]);
+/* Diagnostics (tests/test_gather_references.py): how fgnn_gather_rows* would launch a gather of `rows` rows of row_bytes
+ * (whole 16-byte chunks: the chunk kernels' path; FGNN_EINVAL otherwise) -- the planner the gathers themselves use, with
+ * the device's figures as arguments (cus compute units, wg_per_cu persistent workgroups per CU -- the stand-alone gathers
+ * use 4 --, unroll 2, 4 or 8 independent loads per lane: a tile is 256 * unroll chunks), so it touches no device.  The chunk
+ * kernels walk tiles with a 32-bit cursor, and a launch is admitted only if chunks + grid * tile <= 2^32; a host-sized
+ * gather beyond that goes in slices, a device-sized one (device_sized != 0) or a masked one without a source index is
+ * refused.  out[4 * k .. 4 * k + 4) = {first row, rows, workgroups, tile} of launch k.  Returns the number of launches
+ * (0 for no rows), FGNN_EINVAL for a refusal, FGNN_ENOSPC when the plan has more than max_launches. */
+int fgnn_debug_gather_plan(size_t rows, size_t row_bytes, int device_sized, int has_src_index, uint32_t src_row_mask,
+                           size_t cus, size_t wg_per_cu, int unroll, uint64_t *out, size_t max_launches);
 /* Diagnostics (tests): the stable (key, value) sort the stateless with-replacement samplers order their seeds with
  * (scan.hip; where the reference calls cub::DeviceRadixSort, cuda_sampling_weighted_khop_prefix.cu:200-215), on its
  * own: n uint32 pairs sorted by key in place, equal keys in their input order.  Allocates its scratch and waits. */

@@ -87,6 +87,37 @@ def test_partition_debug_entry_points_are_declared_exported_bound_and_documented
     assert [int(v) for v in out] == [golden[k] for k in lib.PARTITION_PARAMS]
 
 
+GATHER_DEBUG_ENTRY_POINTS = ["fgnn_debug_gather_plan"]
+
+
+def test_gather_debug_entry_point_is_declared_exported_bound_and_documented(hip_lib):
+    """the planner tests/test_gather_references.py checks the 32-bit tile walk's bound with: in the header, in the
+    library, in the binding's export list with a signature and a wrapper, named where INTEGRATION.md lists the debug
+    entry points -- and it answers without a GPU"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "fgnn-artifacts_amd"))
+    from fgnn_hip import lib
+    declared = _declared("fgnn_hip.h")
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in GATHER_DEBUG_ENTRY_POINTS:
+        assert name in declared and hasattr(hip_lib, name) and name in lib.EXPORTS, name
+        assert name in lib.SIGNATURES, name
+        assert "`%s`" % name in doc, name
+    assert callable(getattr(lib, "debug_gather_plan", None))
+    fn = hip_lib.fgnn_debug_gather_plan
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t,
+                   ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
+    out = (ctypes.c_uint64 * 8)(*([0xDEADBEEF] * 8))
+    # 5000 rows of 512 bytes = 160000 chunks = 157 tiles of 1024: one launch of 157 workgroups
+    assert fn(5000, 512, 0, 1, 0xFFFFFFFF, 256, 4, 4, out, 2) == 1
+    assert [int(v) for v in out] == [0, 5000, 157, 1024] + [0xDEADBEEF] * 4
+    # 2^32 - 1024 rows of one chunk: the walk of 1024 workgroups would wrap; two slices, or a refusal when device-sized
+    assert fn(0xFFFFFC00, 16, 0, 1, 0xFFFFFFFF, 256, 4, 4, out, 2) == 2
+    assert [int(v) for v in out] == [0, 1 << 31, 1024, 1024, 1 << 31, 0xFFFFFC00 - (1 << 31), 1024, 1024]
+    assert fn(0xFFFFFC00, 16, 1, 1, 0xFFFFFFFF, 256, 4, 4, out, 2) == -1
+
+
 def test_version_and_scratch(hip_lib):
     hip_lib.fgnn_version.restype = ctypes.c_char_p
     assert b"gfx950" in hip_lib.fgnn_version()
