@@ -25,6 +25,12 @@ struct ChainState {
   size_t ecap0 = 0;                       // worst-case edges of layer 0 for THIS batch
   bool resolved0 = false, inserted0 = false;
   fgnn::FixTail owed = fgnn::no_fix_tail();  // the remap fix-up the layer-1 fill left for the next launch to carry
+  // A bandwidth-bound feature gather follows this batch's sampling on the same GPU, i.e. while the batch's dedup
+  // launches run, its neighbours' gathers do: known natively, before the chain is enqueued, from the call the batch
+  // came in by (fgnn_sampler_run_batch / _run_batch_cached / _run_range with a feature source).  The launches whose
+  // best shape differs between the two workloads choose by it (partition_fill); every other entry point -- a sampler
+  // process's sample_begin / _end, sample_indexed, the engine -- leaves it false and launches what it always did.
+  bool gather_follows = false;
 };
 
 struct fgnn_sampler {
@@ -421,14 +427,15 @@ int admit_batch(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t n
 // next layer's sampling reads the remapped edges -- and the last layer's goes to the caller or runs at the end.  *owed:
 // the fix-up this fill carries when called, the one it leaves on return
 int fill_layer(fgnn_sampler *s, fgnn_sampler::Slot &sl, fgnn_batch *out, hipStream_t st, long l, size_t ecap,
-               bool inserted, bool resolved, bool table_free, fgnn::FixTail *owed) {
+               bool inserted, bool resolved, bool table_free, fgnn::FixTail *owed, bool gather_follows) {
   size_t *d_ne = reinterpret_cast<size_t *>(&out->d_meta->num_edge[l]);
   fgnn::FixTail mine = fgnn::no_fix_tail();
   const int r = hashtable_fill_duplicates_ex(sl.ht, sl.tmp_dst, 0, d_ne, ecap, out->row[l], sl.ws, s->ws_bytes, st,
                                              LayerSummary{&out->d_meta->num_dst[l], &out->d_meta->num_src[l],
                                                           &out->d_meta->num_input},
                                              inserted, nullptr, /*final_fill=*/l == 0, resolved, &mine, owed,
-                                             table_free && l != 0);  // (the last fill decides for itself: nothing follows it)
+                                             table_free && l != 0,  // (the last fill decides for itself: nothing follows it)
+                                             gather_follows);
   *owed = mine;
   return r;
 }
@@ -561,7 +568,7 @@ int sample_chain(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t 
       cs->inserted0 = inserted;
       break;
     }
-    rc = fill_layer(s, sl, out, st, l, ecap, inserted, resolved, table_free, &cs->owed);
+    rc = fill_layer(s, sl, out, st, l, ecap, inserted, resolved, table_free, &cs->owed, cs->gather_follows);
     if (rc != FGNN_OK) return rc;
     in_cap += ecap;
     cur = out->input_nodes;
@@ -580,7 +587,7 @@ int sample_tail(fgnn_sampler *s, uint64_t seq, fgnn_batch *out, hipStream_t st, 
   fgnn::ScanErrorSink sink(&out->d_meta->overflow);
   int rc = FGNN_OK;
   if (cs.ran) {
-    rc = fill_layer(s, sl, out, st, 0, cs.ecap0, cs.inserted0, cs.resolved0, false, &cs.owed);
+    rc = fill_layer(s, sl, out, st, 0, cs.ecap0, cs.inserted0, cs.resolved0, false, &cs.owed, cs.gather_follows);
     if (rc != FGNN_OK) return rc;
   }
   if (cs.owed.mapped) {
@@ -618,14 +625,36 @@ int finish_sampling(fgnn_sampler *s, uint64_t seq, fgnn_batch *out, const uint32
 
 // a whole batch: chain and tail back to back [+ the cache split]
 int sample_batch(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
-                 fgnn_batch *out, const uint32_t *cache_table, void *stream) {
+                 fgnn_batch *out, const uint32_t *cache_table, void *stream, bool gather_follows = false) {
   int rc = admit_batch(s, seq, d_seeds, num_seeds, out);
   if (rc != FGNN_OK) return rc;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   SeqGuard guard = SeqGuard::for_chain(s, seq, st);
   ChainState cs;
+  cs.gather_follows = gather_follows;
   rc = sample_chain(s, seq, d_seeds, num_seeds, batch_key, out, st, guard, &cs);
   return rc == FGNN_OK ? finish_sampling(s, seq, out, cache_table, st, guard, cs) : rc;
+}
+
+// the chain half of a batch as a call of its own; its tail (fgnn_sampler_sample_end) finds the state in the slot
+int sample_begin(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
+                 fgnn_batch *out, void *stream, bool gather_follows) {
+  int rc = admit_batch(s, seq, d_seeds, num_seeds, out);
+  if (rc != FGNN_OK) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  SeqGuard guard = SeqGuard::for_chain(s, seq, st);
+  ChainState cs;
+  cs.gather_follows = gather_follows;
+  rc = sample_chain(s, seq, d_seeds, num_seeds, batch_key, out, st, guard, &cs);
+  if (rc != FGNN_OK) return rc;
+  fgnn_sampler::Slot::Pend &pend = s->slot[seq % kSlots].pend;
+  pend.active = true;
+  pend.seq = seq;
+  pend.out = out;
+  pend.st = st;
+  pend.chain = cs;
+  guard.detach();
+  return launch_status(__func__);
 }
 
 }  // namespace
@@ -647,21 +676,7 @@ extern "C" int fgnn_sampler_sample(fgnn_sampler *s, const uint32_t *d_seeds, siz
 // extraction / message pack and fgnn_batch_finish on the same stream.
 extern "C" int fgnn_sampler_sample_begin_ordered(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds,
                                                  size_t num_seeds, uint64_t batch_key, fgnn_batch *out, void *stream) {
-  int rc = admit_batch(s, seq, d_seeds, num_seeds, out);
-  if (rc != FGNN_OK) return rc;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  SeqGuard guard = SeqGuard::for_chain(s, seq, st);
-  ChainState cs;
-  rc = sample_chain(s, seq, d_seeds, num_seeds, batch_key, out, st, guard, &cs);
-  if (rc != FGNN_OK) return rc;
-  fgnn_sampler::Slot::Pend &pend = s->slot[seq % kSlots].pend;
-  pend.active = true;
-  pend.seq = seq;
-  pend.out = out;
-  pend.st = st;
-  pend.chain = cs;
-  guard.detach();
-  return launch_status(__func__);
+  return sample_begin(s, seq, d_seeds, num_seeds, batch_key, out, stream, /*gather_follows=*/false);
 }
 
 extern "C" int fgnn_sampler_sample_begin(fgnn_sampler *s, const uint32_t *d_seeds, size_t num_seeds, uint64_t batch_key,
@@ -696,7 +711,7 @@ extern "C" int fgnn_sampler_sample_indexed(fgnn_sampler *s, const uint32_t *d_se
 extern "C" int fgnn_sampler_run_batch(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t num_seeds,
                                       uint64_t batch_key, fgnn_batch *out, const uint32_t *cache_table,
                                       const void *feat, const void *label, void *stream) {
-  int rc = sample_batch(s, seq, d_seeds, num_seeds, batch_key, out, cache_table, stream);
+  int rc = sample_batch(s, seq, d_seeds, num_seeds, batch_key, out, cache_table, stream, /*gather_follows=*/feat != nullptr);
   if (rc == FGNN_OK && (feat || label)) rc = fgnn_batch_extract(out, feat, label, stream);
   if (rc == FGNN_OK) rc = fgnn_batch_finish(out, stream);
   return rc;
@@ -914,7 +929,8 @@ extern "C" int fgnn_sampler_run_batch_cached(fgnn_sampler *s, uint64_t seq, cons
                                              const void *cache_rows, const void *full_feat, const void *label,
                                              void *stream) {
   if (!cache_table) return FGNN_EINVAL;
-  int rc = sample_batch(s, seq, d_seeds, num_seeds, batch_key, out, cache_table, stream);
+  int rc = sample_batch(s, seq, d_seeds, num_seeds, batch_key, out, cache_table, stream,
+                        /*gather_follows=*/cache_rows || full_feat);
   if (rc == FGNN_OK) rc = fgnn_batch_extract_cached(out, cache_rows, full_feat, label, stream);
   if (rc == FGNN_OK) rc = fgnn_batch_finish(out, stream);
   return rc;
@@ -953,6 +969,8 @@ extern "C" int fgnn_sampler_run_range(fgnn_sampler *s, const fgnn_run_plan *p, u
   // khop2's cross-batch chain waits for the host, not for the GPU.  Needs a second buffer (the tail of batch i - 1 is
   // still owed when batch i starts)
   const bool pipelined = p->num_batches >= 2;
+  // the stage-only plan of a sampler process carries no feature source: its batches keep the stand-alone shapes
+  const bool gather_follows = p->cached ? (p->cache_rows || p->full_feat) : p->feat != nullptr;
   constexpr uint64_t kNone = ~0ull;
   uint64_t owed_rest = kNone;  // the batch whose chain is enqueued and whose tail is not
   auto rest = [&](uint64_t i) -> int {  // tail + cache split + extraction + finish of batch i
@@ -973,7 +991,7 @@ extern "C" int fgnn_sampler_run_range(fgnn_sampler *s, const fgnn_run_plan *p, u
     void *st = p->streams[i % p->num_streams];
     const auto t0 = std::chrono::steady_clock::now();
     if (pipelined) {
-      rc = fgnn_sampler_sample_begin_ordered(s, i, p->d_train + b0, n, step, b, st);
+      rc = sample_begin(s, i, p->d_train + b0, n, step, b, st, gather_follows);
       if (rc == FGNN_OK) {
         if (owed_rest != kNone) rc = rest(owed_rest);
         owed_rest = i;

@@ -709,7 +709,10 @@ int hashtable_fill_duplicates_ex(fgnn_hashtable *ht, const uint32_t *items, size
                                  size_t ws_bytes, void *stream, LayerSummary summary, bool already_inserted,
                                  ScanWsHost *scan, bool final_fill = false, bool resolved = false,
                                  FixTail *owed_fix = nullptr, const FixTail *carry_fix = nullptr,
-                                 bool table_free = false);
+                                 bool table_free = false, bool gather_follows = false);
+// gather_follows: the batch driver knows that a bandwidth-bound feature gather of this or a neighbouring batch runs on
+// the same GPU while this fill does (engine.hip, fgnn_sampler_run_batch / _run_range with a feature source); the
+// partitioned fill then launches the shapes that win in that mix (partition_fill).  Results do not depend on it.
 // table_free: nothing after this fill reads the global table (no fused sampler insert, no fgnn_hashtable_map, and every
 // later fill of the batch is table_free or final too) -- the fill may then go through the partitioned path although it
 // is not the batch's last (the batch driver's samplers that do not insert themselves: every layer).  The promise is
@@ -732,7 +735,8 @@ PartWs *partition_create(size_t max_items, size_t max_fill_items);
 void partition_destroy(PartWs *w);
 bool partition_fits(const PartWs *w, const fgnn_hashtable *ht, size_t cap);
 int partition_fill(PartWs *w, const fgnn_hashtable *ht, const uint32_t *items, size_t num_items,
-                   const size_t *d_num_items, size_t cap, uint32_t *pos, hipStream_t s, const FixTail &carry);
+                   const size_t *d_num_items, size_t cap, uint32_t *pos, hipStream_t s, const FixTail &carry,
+                   bool gather_follows = false);
 // can the last fill of `cap` items go through the resolving insert (disp[] allocated, one-launch count+assign)?
 bool hashtable_can_resolve(const fgnn_hashtable *ht, size_t cap);
 // Reset as the batch driver uses it: generation bump (wipe only on wrap), optionally without touching the counts

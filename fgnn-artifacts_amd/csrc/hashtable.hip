@@ -554,7 +554,7 @@ int fgnn::hashtable_fill_duplicates_ex(fgnn_hashtable *ht, const uint32_t *items
                                        const size_t *d_num_items, size_t num_items_cap, uint32_t *mapped, void *ws,
                                        size_t ws_bytes, void *stream, LayerSummary summary, bool already_inserted,
                                        ScanWsHost *scan, bool final_fill, bool resolved, FixTail *owed_fix,
-                                       const FixTail *carry_fix, bool table_free) {
+                                       const FixTail *carry_fix, bool table_free, bool gather_follows) {
   if (!ht) return FGNN_EINVAL;
   if (owed_fix) *owed_fix = no_fix_tail();  // mapped != null on return: the caller owes this fill's fix-up
   FixTail carry = carry_fix && carry_fix->mapped ? *carry_fix : no_fix_tail();
@@ -588,7 +588,7 @@ int fgnn::hashtable_fill_duplicates_ex(fgnn_hashtable *ht, const uint32_t *items
       partition_fits(ht->part, ht, cap) && count_assign_grid(cap, scan) > 0) {
     // the batch's last fill (or any fill of a batch that never reads the table): partitioned by hash, deduplicated in
     // LDS, the global table untouched
-    const int rc = partition_fill(ht->part, ht, items, num_items, d_num_items, cap, pos, s, carry);
+    const int rc = partition_fill(ht->part, ht, items, num_items, d_num_items, cap, pos, s, carry, gather_follows);
     if (rc != FGNN_OK) return rc;
     exact = true;
   } else if (!already_inserted) {

@@ -43,8 +43,9 @@ namespace fgnn {
 namespace {
 
 constexpr int kPartThreads = 1024;                // hist / scatter workgroup: 16 waves, 4 items per thread and tile
-constexpr int kPartIPT = 4;
-constexpr int kPartTile = kPartThreads * kPartIPT;  // 4096 items per tile
+constexpr int kPartThreadsShared = 256;           // ... of a batch whose feature gather shares the GPU (gather_follows): 4
+                                                  // waves, 16 items per thread -- same tiles, same bins, same outputs
+constexpr int kPartTile = 4096;                   // items per tile, whatever the workgroup size
 constexpr int kPartMaxBlocks = 128;               // hist / scatter workgroups (rows of the count matrix)
 constexpr int kPartDedupThreads = 512;
 constexpr int kPartRegPairs = 8;                  // pairs a dedup lane keeps in registers: bins up to 4096 items
@@ -98,7 +99,8 @@ __device__ __forceinline__ void part_item(uint32_t t, uint32_t K, const uint32_t
 
 // counts[k][b] = items of bin b among workgroup k's tiles.  Plain stores of the whole row (zeros included): nothing to
 // clear between fills, no atomics, and the scatter's offsets are a pure function of the matrix (deterministic layout).
-__global__ __launch_bounds__(kPartThreads) void part_hist_kernel(const uint32_t *__restrict__ items, size_t n_host,
+template <int T>
+__global__ __launch_bounds__(T) void part_hist_kernel(const uint32_t *__restrict__ items, size_t n_host,
                                                                  const size_t *d_n, size_t cap,
                                                                  const uint32_t *__restrict__ n2o,
                                                                  uint32_t *d_num_items, uint32_t pend, PartView p,
@@ -107,6 +109,7 @@ __global__ __launch_bounds__(kPartThreads) void part_hist_kernel(const uint32_t 
     run_fix_tail(fix, own_blocks);
     return;
   }
+  constexpr int IPT = kPartTile / T;
   __shared__ uint32_t hist[1u << kPartMaxLog2];
   const uint32_t n = (uint32_t)resolve_count64(n_host, d_n, cap);
   const uint32_t K = d_num_items[0];
@@ -114,31 +117,34 @@ __global__ __launch_bounds__(kPartThreads) void part_hist_kernel(const uint32_t 
   const uint32_t total = n + K;
   const uint32_t lg = part_log2(total, p.max_log2), B = 1u << lg;
   if (blockIdx.x >= part_blocks(total, own_blocks)) return;  // no tile: the scatter does not read this row
-  for (uint32_t b = threadIdx.x; b < B; b += kPartThreads) hist[b] = 0;
+  for (uint32_t b = threadIdx.x; b < B; b += T) hist[b] = 0;
   __syncthreads();
   for (uint32_t t0 = blockIdx.x * kPartTile; t0 < total; t0 += own_blocks * kPartTile) {
-    uint32_t key[kPartIPT], val;
+    uint32_t key[IPT], val;
 #pragma unroll
-    for (int r = 0; r < kPartIPT; ++r) {
-      const uint32_t t = t0 + r * kPartThreads + threadIdx.x;
+    for (int r = 0; r < IPT; ++r) {
+      const uint32_t t = t0 + r * T + threadIdx.x;
       key[r] = FGNN_EMPTY_KEY;
       if (t < total) part_item(t, K, n2o, items, pend, &key[r], &val);
     }
 #pragma unroll
-    for (int r = 0; r < kPartIPT; ++r)
-      if (t0 + r * kPartThreads + threadIdx.x < total) atomicAdd(&hist[(key[r] * kPartHash) >> (32 - lg)], 1u);
+    for (int r = 0; r < IPT; ++r)
+      if (t0 + r * T + threadIdx.x < total) atomicAdd(&hist[(key[r] * kPartHash) >> (32 - lg)], 1u);
   }
   __syncthreads();
   uint32_t *row = p.counts + ((size_t)blockIdx.x << lg);
-  for (uint32_t b = threadIdx.x; b < B; b += kPartThreads) row[b] = hist[b];
+  for (uint32_t b = threadIdx.x; b < B; b += T) row[b] = hist[b];
 }
 
-__global__ __launch_bounds__(kPartThreads) void part_scatter_kernel(const uint32_t *__restrict__ items, size_t n_host,
+template <int T>
+__global__ __launch_bounds__(T) void part_scatter_kernel(const uint32_t *__restrict__ items, size_t n_host,
                                                                     const size_t *d_n, size_t cap,
                                                                     const uint32_t *__restrict__ n2o,
                                                                     const uint32_t *d_num_items, uint32_t pend,
                                                                     PartView p, uint32_t *__restrict__ pos) {
-  constexpr int NW = kPartThreads / kWave;
+  constexpr int NW = T / kWave;
+  constexpr int IPT = kPartTile / T;
+  constexpr uint32_t kPer = (1u << kPartMaxLog2) / T;  // bins a thread owns at most: 2 (1024 threads) or 8 (256)
   __shared__ uint32_t off[1u << kPartMaxLog2], cnt[1u << kPartMaxLog2], lbase[1u << kPartMaxLog2];
   __shared__ uint2 stage[kPartTile];
   __shared__ uint32_t sh[NW];
@@ -149,11 +155,11 @@ __global__ __launch_bounds__(kPartThreads) void part_scatter_kernel(const uint32
   const uint32_t nblk = part_blocks(total, gridDim.x);
   if (blockIdx.x >= nblk) return;
   // the first tile's items: their loads go out together with the matrix loads below (one memory round trip)
-  uint32_t key[kPartIPT], val[kPartIPT];
+  uint32_t key[IPT], val[IPT];
   uint32_t t0 = blockIdx.x * kPartTile;
 #pragma unroll
-  for (int r = 0; r < kPartIPT; ++r) {
-    const uint32_t t = t0 + r * kPartThreads + threadIdx.x;
+  for (int r = 0; r < IPT; ++r) {
+    const uint32_t t = t0 + r * T + threadIdx.x;
     key[r] = FGNN_EMPTY_KEY;
     val[r] = 0;
     if (t < total) part_item(t, K, n2o, items, pend, &key[r], &val[r]);
@@ -162,18 +168,18 @@ __global__ __launch_bounds__(kPartThreads) void part_scatter_kernel(const uint32
     if (t < total && t >= K) pos[t - K] = kPartIsOwner;
   }
   // where this workgroup's run of bin b starts = items of bins below b (all workgroups) + items of bin b in the
-  // workgroups before this one: column sums over the count matrix (nblk rows of B cells).  A lane takes one bin (two
-  // when B = 2048) and every G-th row, G = lanes per bin: its loads are independent, a wave reads 64 consecutive cells
+  // workgroups before this one: column sums over the count matrix (nblk rows of B cells).  A lane takes one bin (B / T
+  // bins when B > T) and every G-th row, G = lanes per bin: its loads are independent, a wave reads 64 consecutive cells
   // of a row, the partial sums stay in registers and meet in LDS with one add per lane.
-  for (uint32_t b = threadIdx.x; b < B; b += kPartThreads) {
+  for (uint32_t b = threadIdx.x; b < B; b += T) {
     off[b] = 0;  // bin b in the workgroups before this one
     cnt[b] = 0;  // bin b in all workgroups
   }
   __syncthreads();
   {
-    const uint32_t bc = B < (uint32_t)kPartThreads ? B : (uint32_t)kPartThreads;  // bins side by side
-    const uint32_t G = kPartThreads / bc, g = threadIdx.x / bc, b0 = threadIdx.x % bc;
-    for (uint32_t b = b0; b < B; b += kPartThreads) {  // one trip, two when B = 2048
+    const uint32_t bc = B < (uint32_t)T ? B : (uint32_t)T;  // bins side by side
+    const uint32_t G = T / bc, g = threadIdx.x / bc, b0 = threadIdx.x % bc;
+    for (uint32_t b = b0; b < B; b += T) {  // B / T trips when B > T (1024 threads: two at B = 2048; 256: up to eight)
       uint32_t all = 0, before = 0;
       for (uint32_t k0 = g; k0 < nblk; k0 += 8 * G) {
         uint32_t c[8];
@@ -194,17 +200,18 @@ __global__ __launch_bounds__(kPartThreads) void part_scatter_kernel(const uint32
     __syncthreads();
     // thread j owns bins j*per .. j*per+per-1 (consecutive, so that the block scan of the per-thread totals gives the
     // bin bases)
-    const uint32_t per = (B + kPartThreads - 1) / kPartThreads;  // 1 or 2
-    uint32_t tot_b[2] = {0, 0};
+    const uint32_t per = (B + T - 1) / T;  // <= kPer
+    uint32_t tot_b[kPer], mine = 0;
 #pragma unroll
-    for (uint32_t q = 0; q < 2; ++q) {
+    for (uint32_t q = 0; q < kPer; ++q) {
       const uint32_t b = threadIdx.x * per + q;
-      if (q < per && b < B) tot_b[q] = cnt[b];
+      tot_b[q] = q < per && b < B ? cnt[b] : 0u;
+      mine += tot_b[q];
     }
     uint32_t tot;
-    uint32_t run = block_exclusive_scan<NW>(tot_b[0] + tot_b[1], sh, &tot);
+    uint32_t run = block_exclusive_scan<NW>(mine, sh, &tot);
 #pragma unroll
-    for (uint32_t q = 0; q < 2; ++q) {
+    for (uint32_t q = 0; q < kPer; ++q) {
       const uint32_t b = threadIdx.x * per + q;
       if (q < per && b < B) {
         off[b] += run;
@@ -217,31 +224,32 @@ __global__ __launch_bounds__(kPartThreads) void part_scatter_kernel(const uint32
   // Per tile: rank every item inside its bin (LDS add), order the tile by bin in an LDS stage, write it out in that
   // order -- consecutive lanes then store consecutive pairs of a bin's run (a wave covers a handful of runs) instead of
   // 64 scattered 8-byte stores per wave instruction.
-  const uint32_t per = (B + kPartThreads - 1) / kPartThreads;
+  const uint32_t per = (B + T - 1) / T;
   for (;;) {
-    for (uint32_t b = threadIdx.x; b < B; b += kPartThreads) cnt[b] = 0;
+    for (uint32_t b = threadIdx.x; b < B; b += T) cnt[b] = 0;
     __syncthreads();  // off[] complete (first round) / advanced (later rounds), cnt[] zero
-    uint32_t where[kPartIPT];  // bin << 16 | rank inside the tile's run of the bin
+    uint32_t where[IPT];  // bin << 16 | rank inside the tile's run of the bin
 #pragma unroll
-    for (int r = 0; r < kPartIPT; ++r) {
+    for (int r = 0; r < IPT; ++r) {
       where[r] = 0;
-      if (t0 + r * kPartThreads + threadIdx.x < total) {
+      if (t0 + r * T + threadIdx.x < total) {
         const uint32_t b = (key[r] * kPartHash) >> (32 - lg);
         where[r] = (b << 16) | atomicAdd(&cnt[b], 1u);  // rank < 4096
       }
     }
     __syncthreads();
     {  // lbase[b] = items of the tile in bins below b
-      uint32_t c2[2] = {0, 0};
+      uint32_t c2[kPer], mine = 0;
 #pragma unroll
-      for (uint32_t q = 0; q < 2; ++q) {
+      for (uint32_t q = 0; q < kPer; ++q) {
         const uint32_t b = threadIdx.x * per + q;
-        if (q < per && b < B) c2[q] = cnt[b];
+        c2[q] = q < per && b < B ? cnt[b] : 0u;
+        mine += c2[q];
       }
       uint32_t tot;
-      uint32_t run = block_exclusive_scan<NW>(c2[0] + c2[1], sh, &tot);
+      uint32_t run = block_exclusive_scan<NW>(mine, sh, &tot);
 #pragma unroll
-      for (uint32_t q = 0; q < 2; ++q) {
+      for (uint32_t q = 0; q < kPer; ++q) {
         const uint32_t b = threadIdx.x * per + q;
         if (q < per && b < B) {
           lbase[b] = run;
@@ -251,14 +259,14 @@ __global__ __launch_bounds__(kPartThreads) void part_scatter_kernel(const uint32
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < kPartIPT; ++r)
-      if (t0 + r * kPartThreads + threadIdx.x < total)
+    for (int r = 0; r < IPT; ++r)
+      if (t0 + r * T + threadIdx.x < total)
         stage[lbase[where[r] >> 16] + (where[r] & 0xffffu)] = make_uint2(key[r], val[r]);
     __syncthreads();
     const uint32_t in_tile = total - t0 < (uint32_t)kPartTile ? total - t0 : (uint32_t)kPartTile;
 #pragma unroll
-    for (int r = 0; r < kPartIPT; ++r) {
-      const uint32_t i = r * kPartThreads + threadIdx.x;
+    for (int r = 0; r < IPT; ++r) {
+      const uint32_t i = r * T + threadIdx.x;
       if (i < in_tile) {
         const uint2 kv = stage[i];
         const uint32_t b = (kv.x * kPartHash) >> (32 - lg);
@@ -268,10 +276,10 @@ __global__ __launch_bounds__(kPartThreads) void part_scatter_kernel(const uint32
     t0 += gridDim.x * kPartTile;
     if (t0 >= total) break;  // uniform
     __syncthreads();  // every off[] / lbase[] / stage[] read done
-    for (uint32_t b = threadIdx.x; b < B; b += kPartThreads) off[b] += cnt[b];
+    for (uint32_t b = threadIdx.x; b < B; b += T) off[b] += cnt[b];
 #pragma unroll
-    for (int r = 0; r < kPartIPT; ++r) {
-      const uint32_t t = t0 + r * kPartThreads + threadIdx.x;
+    for (int r = 0; r < IPT; ++r) {
+      const uint32_t t = t0 + r * T + threadIdx.x;
       key[r] = FGNN_EMPTY_KEY;
       val[r] = 0;
       if (t < total) part_item(t, K, n2o, items, pend, &key[r], &val[r]);
@@ -457,7 +465,8 @@ bool partition_fits(const PartWs *w, const fgnn_hashtable *ht, size_t cap) {
 }
 
 int partition_fill(PartWs *w, const fgnn_hashtable *ht, const uint32_t *items, size_t num_items,
-                   const size_t *d_num_items, size_t cap, uint32_t *pos, hipStream_t s, const FixTail &carry) {
+                   const size_t *d_num_items, size_t cap, uint32_t *pos, hipStream_t s, const FixTail &carry,
+                   bool gather_follows) {
   const HtView tv = ht_view(ht);
   PartView p{w->pairs, w->bins, w->bins + (size_t)kPartMaxBlocks * w->max_bins, w->max_log2,
              g_part_lds_limit.load(std::memory_order_relaxed) >= 0
@@ -466,11 +475,24 @@ int partition_fill(PartWs *w, const fgnn_hashtable *ht, const uint32_t *items, s
   const size_t tiles = div_up(cap + ht->max_items, (size_t)kPartTile);
   const size_t blocks = tiles < (size_t)kPartMaxBlocks ? tiles : (size_t)kPartMaxBlocks;
   const size_t bins_grid = w->max_bins < (size_t)device_cu_count() * 2 ? w->max_bins : (size_t)device_cu_count() * 2;
-  // (the fix-up tail's workgroups run with this launch's 1024 threads: run_fix_tail strides by blockDim)
-  hipLaunchKernelGGL(part_hist_kernel, dim3((unsigned)(blocks + carry.blocks)), dim3(kPartThreads), 0, s, items,
-                     num_items, d_num_items, cap, ht->n2o, ht->d_num_items, tv.pend, p, (uint32_t)blocks, carry);
-  hipLaunchKernelGGL(part_scatter_kernel, dim3((unsigned)blocks), dim3(kPartThreads), 0, s, items, num_items,
-                     d_num_items, cap, ht->n2o, ht->d_num_items, tv.pend, p, pos);
+  // Workgroups of 1024 threads are what the two launches like best alone (a sampler GPU: the sampler-side stage takes
+  // 0.0677 ms per batch against 0.0721 at 256, profiles/r05_g_mix_traces.txt).  Beside other batches' bandwidth-bound
+  // feature gathers it is the other way round: whole path 0.1030 -> 0.1001 and 0.1037 -> 0.1015 ms per batch in two
+  // sessions, the stage alone unchanged because it never takes this branch (profiles/r09_a_ab.txt, r09_b_ab.txt).  Same tiles, same bins, same
+  // outputs either way.  (FGNN_TAIL_PART256=0, profiling build: A/B switch)
+  // (the fix-up tail's workgroups run with this launch's threads: run_fix_tail strides by blockDim)
+  const unsigned hist_grid = (unsigned)(blocks + carry.blocks);
+  if (gather_follows && tune_int("FGNN_TAIL_PART256", 1) != 0) {
+    hipLaunchKernelGGL(part_hist_kernel<kPartThreadsShared>, dim3(hist_grid), dim3(kPartThreadsShared), 0, s, items,
+                       num_items, d_num_items, cap, ht->n2o, ht->d_num_items, tv.pend, p, (uint32_t)blocks, carry);
+    hipLaunchKernelGGL(part_scatter_kernel<kPartThreadsShared>, dim3((unsigned)blocks), dim3(kPartThreadsShared), 0, s,
+                       items, num_items, d_num_items, cap, ht->n2o, ht->d_num_items, tv.pend, p, pos);
+  } else {
+    hipLaunchKernelGGL(part_hist_kernel<kPartThreads>, dim3(hist_grid), dim3(kPartThreads), 0, s, items, num_items,
+                       d_num_items, cap, ht->n2o, ht->d_num_items, tv.pend, p, (uint32_t)blocks, carry);
+    hipLaunchKernelGGL(part_scatter_kernel<kPartThreads>, dim3((unsigned)blocks), dim3(kPartThreads), 0, s, items,
+                       num_items, d_num_items, cap, ht->n2o, ht->d_num_items, tv.pend, p, pos);
+  }
   // more than the 64 KiB a kernel gets without asking (160 KiB per CU on gfx950).  The attribute belongs to the
   // function ON A DEVICE: asked once per device (a process that samples on a second GPU launches there too)
   static std::atomic<bool> attr_done[kMaxAttrDevices];
