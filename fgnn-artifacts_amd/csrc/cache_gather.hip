@@ -16,7 +16,7 @@
 //    length is not a multiple of 16 (labels: dim 1 x 8 B).
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
+#include <type_traits>
 
 #include "fgnn_device.h"
 
@@ -47,6 +47,31 @@ __global__ __launch_bounds__(kBlock) void cache_count_kernel(const uint32_t *__r
   if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
+// One 256-node round of the split: node i = row0 + threadIdx.x is ranked among the round's misses and written to its
+// list -- a miss at miss_before + its rank, a hit at the number of hits before it (items before i - misses before i).
+// hit_slot(i) is the cache slot of a hit.  `write` = false: rank only.  Returns the round's miss count.
+template <typename HitSlot>
+__device__ __forceinline__ uint32_t split_round(size_t row0, bool write, bool is_miss, uint32_t miss_before, uint32_t *sh,
+                                                const uint32_t *__restrict__ nodes, uint32_t *__restrict__ miss_src,
+                                                uint32_t *__restrict__ miss_dst, uint32_t *__restrict__ cache_src,
+                                                uint32_t *__restrict__ cache_dst, HitSlot hit_slot) {
+  const size_t i = row0 + threadIdx.x;
+  uint32_t tot;
+  const uint32_t mrank = block_exclusive_rank<kWavesPerBlock>(is_miss, sh, &tot);
+  if (write) {
+    if (is_miss) {
+      const uint32_t p = miss_before + mrank;
+      miss_dst[p] = (uint32_t)i;
+      miss_src[p] = nodes[i];
+    } else {
+      const uint32_t p = (uint32_t)(row0 - miss_before) + (threadIdx.x - mrank);
+      cache_dst[p] = (uint32_t)i;
+      cache_src[p] = hit_slot(i);
+    }
+  }
+  return tot;
+}
+
 template <int IPT>
 __global__ __launch_bounds__(kBlock) void cache_split_kernel(const uint32_t *__restrict__ nodes, size_t n_host,
                                                              const uint32_t *d_n, size_t cap,
@@ -71,21 +96,8 @@ __global__ __launch_bounds__(kBlock) void cache_split_kernel(const uint32_t *__r
       s = slot[i];
       is_miss = (s == FGNN_EMPTY_KEY);
     }
-    uint32_t tot;
-    const uint32_t mrank = block_exclusive_rank<kWavesPerBlock>(is_miss, sh, &tot);
-    if (i < n) {
-      if (is_miss) {
-        const uint32_t p = miss_before + mrank;
-        miss_dst[p] = (uint32_t)i;
-        miss_src[p] = nodes[i];
-      } else {
-        // hits before i = items before i - misses before i
-        const uint32_t p = (uint32_t)(row0 - miss_before) + (threadIdx.x - mrank);
-        cache_dst[p] = (uint32_t)i;
-        cache_src[p] = s;
-      }
-    }
-    miss_before += tot;
+    miss_before += split_round(row0, i < n, is_miss, miss_before, sh, nodes, miss_src, miss_dst, cache_src, cache_dst,
+                               [s](size_t) { return s; });
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const uint32_t m = *d_total_miss;
@@ -177,68 +189,34 @@ __global__ __launch_bounds__(kBlock) void cache_split_fused_kernel(const uint32_
     const size_t row0 = chunk0 + (size_t)r * kBlock;
     const size_t i = row0 + threadIdx.x;
     const bool is_miss = (miss_mask >> r) & 1u;
-    uint32_t t2;
-    const uint32_t mrank = block_exclusive_rank<kWavesPerBlock>(is_miss, sh, &t2);
-    if (i < n && !(ablate & 4u)) {
-      if (is_miss) {
-        const uint32_t p = miss_before + mrank;
-        miss_dst[p] = (uint32_t)i;
-        miss_src[p] = nodes[i];
-      } else {
-        const uint32_t p = (uint32_t)(row0 - miss_before) + (threadIdx.x - mrank);
-        cache_dst[p] = (uint32_t)i;
-        cache_src[p] = slot[i];
-      }
-    }
-    miss_before += t2;
+    miss_before += split_round(row0, i < n && !(ablate & 4u), is_miss, miss_before, sh, nodes, miss_src, miss_dst,
+                               cache_src, cache_dst, [slot](size_t at) { return slot[at]; });
   }
   phase_mark(scan, tile, 3);
 }
 
 struct alignas(16) chunk16 { uint32_t a, b, c, d; };
+// Where a logical row of a gather is written and read.  (The order in which a row map reads its two index arrays
+// decides how the compiler schedules the walk: gather_rows16_kernel reads the source index first, gather_band the
+// destination -- with the source first there, the hit list's row loads of extract_fused_kernel<*, *, 32 | 64> came out
+// one after the other and its HBM band took 0.24 ms instead of 0.15.  Look at the ISA of both after a change here.)
+struct RowPair { size_t dst, src; };
 
-// flat 16-byte-chunk gather; chunks_per_row = row_bytes / 16.  A workgroup walks tiles of
-// kBlock*UNROLL consecutive chunks (chunk c of the output = chunk c%cpr of row c/cpr).  The grid is capped
-// at a few workgroups per CU: enough loads in flight to saturate HBM while leaving wave slots for the
-// latency-bound sampling kernels of the next batch that run concurrently on another stream.
-// CPR > 0 fixes chunks-per-row at compile time (the index division becomes a multiply/shift).
-// `tail` (batch driver): the batch's label rows and its 128-byte summary ride along with the feature gather instead of
-// taking a launch each (a 4 us element gather and a 4 us copyBuffer behind 6 us event gaps, per batch)
-template <int UNROLL, int CPR, bool NT, bool NTS>
-__global__ __launch_bounds__(kBlock) void gather_rows16_kernel(chunk16 *__restrict__ out,
-                                                               const chunk16 *__restrict__ src,
-                                                               const uint32_t *__restrict__ src_index,
-                                                               const uint32_t *__restrict__ dst_index, size_t n_host,
-                                                               const uint32_t *d_n, size_t cap, uint32_t cpr_rt,
-                                                               uint32_t src_mask, GatherTail tail) {
+// THE chunk walk.  Workgroup `bid` of a band of `nb` moves its share of n rows of 16-byte chunks, chunks_per_row =
+// row_bytes / 16, in tiles of kBlock * UNROLL consecutive chunks (chunk c of the list = chunk c % cpr of row c / cpr), so
+// every lane of a wave is busy for any feature width and UNROLL independent 16-byte loads are in flight per lane before
+// the first store.  rows(r) is the RowPair of logical row r.  CPR > 0 fixes chunks-per-row at compile time (the index
+// division becomes a multiply/shift).  NT / NTS: the full tiles' loads / stores are non-temporal, four 32-bit accesses
+// per chunk.  The cursor is 32 bits wide: see walk_fits for what the host admits.
+template <int UNROLL, int CPR, bool NT, bool NTS, typename RowMap>
+__device__ __forceinline__ void walk_chunks(chunk16 *__restrict__ out, const chunk16 *__restrict__ src, uint32_t n,
+                                            uint32_t cpr_rt, uint32_t bid, uint32_t nb, RowMap rows) {
   const uint32_t cpr = CPR ? (uint32_t)CPR : cpr_rt;
-  const bool stamped = tail.stamps != nullptr && blockIdx.x < kGatherStampBlocks;
-  if (stamped && threadIdx.x == 0) {
-    tail.stamps[2 * blockIdx.x] = wall_clock64();
-    if (blockIdx.x == 0) tail.stamps[2 * kGatherStampBlocks] = gridDim.x;
-  }
-  if (tail.label_out) {
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < tail.num_label; i += stride) {
-      const size_t r = tail.label_index[i];
-      switch (tail.label_esz) {
-        case 1: static_cast<uint8_t *>(tail.label_out)[i] = static_cast<const uint8_t *>(tail.label_src)[r]; break;
-        case 2: static_cast<uint16_t *>(tail.label_out)[i] = static_cast<const uint16_t *>(tail.label_src)[r]; break;
-        case 4: static_cast<uint32_t *>(tail.label_out)[i] = static_cast<const uint32_t *>(tail.label_src)[r]; break;
-        default:
-          static_cast<unsigned long long *>(tail.label_out)[i] = static_cast<const unsigned long long *>(tail.label_src)[r];
-      }
-    }
-  }
-  // the summary is final before this launch starts (every kernel that writes it is earlier in the stream)
-  if (tail.meta_dst && blockIdx.x == gridDim.x - 1 && threadIdx.x < tail.meta_words)
-    tail.meta_dst[threadIdx.x] = tail.meta_src[threadIdx.x];
-  const uint32_t n = (uint32_t)resolve_count(n_host, d_n, cap);
-  const uint32_t total = n * cpr;  // the host admits a launch only if cap * cpr + grid * tile <= 2^32 (walk_fits)
+  const uint32_t total = n * cpr;
   constexpr uint32_t tile = kBlock * UNROLL;
   const uint32_t full = total / tile * tile;
-  uint32_t tile0 = blockIdx.x * tile;
-  for (; tile0 < full; tile0 += gridDim.x * tile) {
+  uint32_t tile0 = bid * tile;
+  for (; tile0 < full; tile0 += nb * tile) {
     chunk16 v[UNROLL];
     size_t dsts[UNROLL];
 #pragma unroll
@@ -246,9 +224,8 @@ __global__ __launch_bounds__(kBlock) void gather_rows16_kernel(chunk16 *__restri
       const uint32_t cc = tile0 + u * kBlock + threadIdx.x;
       const uint32_t row = cc / cpr;
       const uint32_t col = cc - row * cpr;
-      const size_t srow = (src_index ? src_index[row] : row) & src_mask;
-      const size_t drow = dst_index ? dst_index[row] : row;
-      const chunk16 *sp = src + srow * cpr + col;
+      const RowPair at = rows(row);
+      const chunk16 *sp = src + at.src * cpr + col;
       if (NT) {
         v[u].a = __builtin_nontemporal_load(&sp->a);
         v[u].b = __builtin_nontemporal_load(&sp->b);
@@ -257,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void gather_rows16_kernel(chunk16 *__restri
       } else {
         v[u] = *sp;
       }
-      dsts[u] = drow * cpr + col;
+      dsts[u] = at.dst * cpr + col;
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
@@ -280,12 +257,60 @@ __global__ __launch_bounds__(kBlock) void gather_rows16_kernel(chunk16 *__restri
       if (cc < total) {
         const uint32_t row = cc / cpr;
         const uint32_t col = cc - row * cpr;
-        const size_t srow = (src_index ? src_index[row] : row) & src_mask;
-        const size_t drow = dst_index ? dst_index[row] : row;
-        out[drow * cpr + col] = src[srow * cpr + col];
+        const RowPair at = rows(row);
+        out[at.dst * cpr + col] = src[at.src * cpr + col];
       }
     }
   }
+}
+
+// out[i] = src[index[i]], elements of type T: the share of workgroup `bid` of a band of `nb`
+template <typename T>
+__device__ __forceinline__ void copy_indexed(void *out, const void *src, const uint32_t *index, uint32_t n, uint32_t bid,
+                                             uint32_t nb) {
+  const uint32_t stride = nb * kBlock;
+  for (uint32_t i = bid * kBlock + threadIdx.x; i < n; i += stride) {
+    const size_t r = index[i];
+    static_cast<T *>(out)[i] = static_cast<const T *>(src)[r];
+  }
+}
+
+// The riders of a batch's last gather launch (GatherTail), over workgroup `bid` of a band of `nb`: the label rows and the
+// 128-byte summary, instead of a launch each (a 4 us element gather and a 4 us copyBuffer behind 6 us event gaps, per batch)
+__device__ __forceinline__ void run_gather_tail(const GatherTail &tail, uint32_t bid, uint32_t nb) {
+  if (tail.label_out) {
+    switch (tail.label_esz) {
+      case 1: copy_indexed<uint8_t>(tail.label_out, tail.label_src, tail.label_index, tail.num_label, bid, nb); break;
+      case 2: copy_indexed<uint16_t>(tail.label_out, tail.label_src, tail.label_index, tail.num_label, bid, nb); break;
+      case 4: copy_indexed<uint32_t>(tail.label_out, tail.label_src, tail.label_index, tail.num_label, bid, nb); break;
+      default: copy_indexed<unsigned long long>(tail.label_out, tail.label_src, tail.label_index, tail.num_label, bid, nb);
+    }
+  }
+  // the summary is final before this launch starts (every kernel that writes it is earlier in the stream)
+  if (tail.meta_dst && bid == nb - 1 && threadIdx.x < tail.meta_words) tail.meta_dst[threadIdx.x] = tail.meta_src[threadIdx.x];
+}
+
+// flat 16-byte-chunk gather: walk_chunks over the whole grid, either index array optional.  The grid is capped at a few
+// workgroups per CU: enough loads in flight to saturate HBM while leaving wave slots for the latency-bound sampling
+// kernels of the next batch that run concurrently on another stream.
+template <int UNROLL, int CPR, bool NT, bool NTS>
+__global__ __launch_bounds__(kBlock) void gather_rows16_kernel(chunk16 *__restrict__ out,
+                                                               const chunk16 *__restrict__ src,
+                                                               const uint32_t *__restrict__ src_index,
+                                                               const uint32_t *__restrict__ dst_index, size_t n_host,
+                                                               const uint32_t *d_n, size_t cap, uint32_t cpr_rt,
+                                                               uint32_t src_mask, GatherTail tail) {
+  const bool stamped = tail.stamps != nullptr && blockIdx.x < kGatherStampBlocks;
+  if (stamped && threadIdx.x == 0) {
+    tail.stamps[2 * blockIdx.x] = wall_clock64();
+    if (blockIdx.x == 0) tail.stamps[2 * kGatherStampBlocks] = gridDim.x;
+  }
+  run_gather_tail(tail, blockIdx.x, gridDim.x);
+  const uint32_t n = (uint32_t)resolve_count(n_host, d_n, cap);
+  walk_chunks<UNROLL, CPR, NT, NTS>(out, src, n, cpr_rt, blockIdx.x, gridDim.x, [=](uint32_t row) {
+    const size_t srow = (src_index ? src_index[row] : row) & src_mask;
+    return RowPair{dst_index ? dst_index[row] : row, srow};
+  });
   if (stamped) {
     __syncthreads();
     if (threadIdx.x == 0) tail.stamps[2 * blockIdx.x + 1] = wall_clock64();
@@ -293,54 +318,15 @@ __global__ __launch_bounds__(kBlock) void gather_rows16_kernel(chunk16 *__restri
 }
 
 // ---- the one-launch trainer-side extraction (ExtractJob, fgnn_device.h) ----------------------------------------------
-// One band of workgroups `bid` of `nb` walking a list's rows as flat 16-byte chunks: the loop of gather_rows16_kernel
-// with both index arrays present, non-temporal loads and stores.
+// One band of workgroups walking a list whose index arrays are both present (no null test per row), non-temporal both ways
 template <int UNROLL, int CPR>
 __device__ __forceinline__ void gather_band(chunk16 *__restrict__ out, const chunk16 *__restrict__ src,
                                             const uint32_t *__restrict__ src_index,
                                             const uint32_t *__restrict__ dst_index, uint32_t n, uint32_t cpr_rt,
                                             uint32_t src_mask, uint32_t bid, uint32_t nb) {
-  const uint32_t cpr = CPR ? (uint32_t)CPR : cpr_rt;
-  const uint32_t total = n * cpr;  // the host admits a job only if cap * cpr + nb * tile <= 2^32 (walk_fits)
-  constexpr uint32_t tile = kBlock * UNROLL;
-  const uint32_t full = total / tile * tile;
-  uint32_t tile0 = bid * tile;
-  for (; tile0 < full; tile0 += nb * tile) {
-    chunk16 v[UNROLL];
-    size_t dsts[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t cc = tile0 + u * kBlock + threadIdx.x;
-      const uint32_t row = cc / cpr;
-      const uint32_t col = cc - row * cpr;
-      const size_t srow = src_index[row] & src_mask;
-      const chunk16 *sp = src + srow * cpr + col;
-      v[u].a = __builtin_nontemporal_load(&sp->a);
-      v[u].b = __builtin_nontemporal_load(&sp->b);
-      v[u].c = __builtin_nontemporal_load(&sp->c);
-      v[u].d = __builtin_nontemporal_load(&sp->d);
-      dsts[u] = (size_t)dst_index[row] * cpr + col;
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      chunk16 *dp = out + dsts[u];
-      __builtin_nontemporal_store(v[u].a, &dp->a);
-      __builtin_nontemporal_store(v[u].b, &dp->b);
-      __builtin_nontemporal_store(v[u].c, &dp->c);
-      __builtin_nontemporal_store(v[u].d, &dp->d);
-    }
-  }
-  if (tile0 == full && full < total) {  // ragged last tile: the workgroup whose turn it is
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t cc = full + u * kBlock + threadIdx.x;
-      if (cc < total) {
-        const uint32_t row = cc / cpr;
-        const uint32_t col = cc - row * cpr;
-        out[(size_t)dst_index[row] * cpr + col] = src[(size_t)(src_index[row] & src_mask) * cpr + col];
-      }
-    }
-  }
+  walk_chunks<UNROLL, CPR, true, true>(out, src, n, cpr_rt, bid, nb, [=](uint32_t row) {
+    return RowPair{dst_index[row], src_index[row] & src_mask};
+  });
 }
 
 struct FusedArgs {
@@ -360,6 +346,7 @@ struct FusedArgs {
   const uint32_t *seg_src[FGNN_MAX_COPY_SEGMENTS];
   uint32_t seg_begin[FGNN_MAX_COPY_SEGMENTS + 1];
 };
+static_assert(std::is_trivially_copyable<FusedArgs>::value, "passed to the kernel by value");
 
 // UL / UH: independent 16-byte loads in flight per lane in the link band / the HBM band
 template <int UL, int UH, int CPR>
@@ -383,22 +370,7 @@ __global__ __launch_bounds__(kBlock) void extract_fused_kernel(const FusedArgs a
     gather_band<UL, CPR>(a.out, a.miss_rows, a.miss_src, a.miss_dst, n_miss, a.cpr, a.miss_mask, bid, a.link_wgs);
   } else {
     const uint32_t nb = gridDim.x - a.link_wgs;
-    const GatherTail &tail = a.tail;
-    if (tail.label_out) {
-      const uint32_t stride = nb * kBlock;
-      for (uint32_t i = bid * kBlock + threadIdx.x; i < tail.num_label; i += stride) {
-        const size_t r = tail.label_index[i];
-        switch (tail.label_esz) {
-          case 1: static_cast<uint8_t *>(tail.label_out)[i] = static_cast<const uint8_t *>(tail.label_src)[r]; break;
-          case 2: static_cast<uint16_t *>(tail.label_out)[i] = static_cast<const uint16_t *>(tail.label_src)[r]; break;
-          case 4: static_cast<uint32_t *>(tail.label_out)[i] = static_cast<const uint32_t *>(tail.label_src)[r]; break;
-          default:
-            static_cast<unsigned long long *>(tail.label_out)[i] = static_cast<const unsigned long long *>(tail.label_src)[r];
-        }
-      }
-    }
-    // the summary is final before this launch starts (every kernel that writes it is earlier in the stream)
-    if (tail.meta_dst && bid == nb - 1 && threadIdx.x < tail.meta_words) tail.meta_dst[threadIdx.x] = tail.meta_src[threadIdx.x];
+    run_gather_tail(a.tail, bid, nb);
     if (a.num_segs) {
       // the table goes to LDS with constant indices into the kernel arguments (a variable index would make the
       // compiler copy them to scratch memory)
@@ -478,6 +450,31 @@ size_t dtype_bytes(int dtype) {
   }
 }
 
+// ---- runtime values as template arguments ------------------------------------------------------------------------------
+// f(std::integral_constant) of the listed value that equals v, of Default if none does
+template <auto Default, auto... Others, typename F>
+void pick(decltype(Default) v, F &&f) {
+  if (!((v == Others && (f(std::integral_constant<decltype(Others), Others>{}), true)) || ...))
+    f(std::integral_constant<decltype(Default), Default>{});
+}
+
+// pick() for a choice only the profiling build can make (tune_int is its default elsewhere): the shipped library
+// instantiates the default alone, so it holds no kernel it cannot launch
+#ifdef FGNN_PROFILING
+constexpr bool kTunable = true;
+#else
+constexpr bool kTunable = false;
+#endif
+template <auto Default, auto... Others, typename F>
+void pick_tuned(decltype(Default) v, F &&f) {
+  if constexpr (kTunable) pick<Default, Others...>(v, f);
+  else f(std::integral_constant<decltype(Default), Default>{});
+}
+
+// THE list of chunks-per-row values with kernels of their own (feature widths 100, 128 and 256 floats); 0: any other
+template <typename F>
+void pick_cpr(uint32_t cpr, F &&f) { pick<0u, 25u, 32u, 64u>(cpr, f); }
+
 }  // namespace
 }  // namespace fgnn
 
@@ -538,21 +535,17 @@ int fgnn::get_miss_cache_index_ex(const uint32_t *table, const uint32_t *nodes, 
     const int rc = hashtable_map_fix(carry, stream);
     if (rc != FGNN_OK) return rc;
   }
-  if (ipt == 1)
-    hipLaunchKernelGGL((cache_count_kernel<1>), dim3(nb), dim3(kBlock), 0, s, table, nodes, num_nodes, d_num_nodes, cap,
-                       slot, sums);
-  else
-    hipLaunchKernelGGL((cache_count_kernel<kItemsPerThread>), dim3(nb), dim3(kBlock), 0, s, table, nodes, num_nodes,
-                       d_num_nodes, cap, slot, sums);
+  pick<kItemsPerThread, 1>(ipt, [&](auto ipt_c) {
+    hipLaunchKernelGGL((cache_count_kernel<ipt_c()>), dim3(nb), dim3(kBlock), 0, s, table, nodes, num_nodes, d_num_nodes,
+                       cap, slot, sums);
+  });
   if (launch_scan_block_sums(sums, nb, nullptr, total, nullptr, nullptr, s, d_num_nodes, (uint32_t)(kBlock * ipt)) !=
       FGNN_OK)
     return FGNN_EHIP;
-  if (ipt == 1)
-    hipLaunchKernelGGL((cache_split_kernel<1>), dim3(nb), dim3(kBlock), 0, s, nodes, num_nodes, d_num_nodes, cap, slot,
-                       sums, total, miss_src, miss_dst, cache_src, cache_dst, d_counts);
-  else
-    hipLaunchKernelGGL((cache_split_kernel<kItemsPerThread>), dim3(nb), dim3(kBlock), 0, s, nodes, num_nodes,
-                       d_num_nodes, cap, slot, sums, total, miss_src, miss_dst, cache_src, cache_dst, d_counts);
+  pick<kItemsPerThread, 1>(ipt, [&](auto ipt_c) {
+    hipLaunchKernelGGL((cache_split_kernel<ipt_c()>), dim3(nb), dim3(kBlock), 0, s, nodes, num_nodes, d_num_nodes, cap,
+                       slot, sums, total, miss_src, miss_dst, cache_src, cache_dst, d_counts);
+  });
   return launch_status(__func__);
 }
 
@@ -575,21 +568,19 @@ extern "C" int fgnn_gather_rows_shared(void *out, const void *src, const uint32_
 }
 
 // ---- the 32-bit walks' bound: ONE admissibility rule, owned by the host ------------------------------------------------
-// gather_rows16_kernel and gather_band walk a list's chunks with a 32-bit cursor: workgroup b starts at b * tile and adds
-// grid * tile while the cursor is below `full` (the chunk total rounded down to whole tiles); the ragged tail belongs to
-// the workgroup whose cursor ends exactly on `full`.  The last addition of a workgroup starts below `total` and lands
-// below total + grid * tile: if that passes 2^32 the cursor wraps to a small value, is below `full` again, and the
-// workgroup starts over -- it never ends (total 0xfffffc00, 1024 workgroups, tile 1024: workgroup 0 is back at tile 0
-// after 4096 steps).  So a launch is admitted only if
-//     total + grid * tile <= 2^32            total = capacity in rows * chunks per row, grid = what the launch really gets
+// walk_chunks walks a list's chunks with a 32-bit cursor: workgroup b starts at b * tile and adds nb * tile while the
+// cursor is below `full` (the chunk total rounded down to whole tiles); the ragged tail belongs to the workgroup whose
+// cursor ends exactly on `full`.  The last addition of a workgroup starts below `total` and lands below total + nb * tile:
+// if that passes 2^32 the cursor wraps to a small value, is below `full` again, and the workgroup starts over -- it never
+// ends (total 0xfffffc00, 1024 workgroups, tile 1024: workgroup 0 is back at tile 0 after 4096 steps).  So a walk is
+// admitted only if
+//     total + nb * tile <= 2^32            total = capacity in rows * chunks per row, nb = the workgroups it really gets
 // and nothing else in this file compares a chunk total with 2^32.  A device-side count only shrinks `total` below the
-// capacity the rule was applied to.  What was checked by reading for the other 32-bit cursors of this file:
-//  * the link band of extract_fused_kernel is gather_band with nb = link_wgs and the link band's own tile (kBlock * UL):
-//    the same walk, the same rule, applied with those two numbers (fused_plan); the HBM band likewise with nb = its
-//    workgroups and kBlock * UH, for the miss list (no link band) and the hit list;
-//  * the label loops (`i += grid * kBlock`, i < num_label) have the cursor's shape without a tail: they wrap -- and
-//    never end -- when num_label + grid * kBlock passes 2^32.  Same rule with rows = num_label, one chunk per row and a
-//    tile of kBlock (job_ok only bounds num_label by 2^32 - 1, which is not enough by itself);
+// capacity the rule was applied to.  Two places call the loop: gather_rows16_kernel with nb = the grid and a tile of
+// kBlock * UNROLL (gather_plan), and extract_fused_kernel through gather_band -- link band: nb = link_wgs, kBlock * UL;
+// HBM band: nb = its workgroups, kBlock * UH (fused_plan).  The other 32-bit cursors of this file, checked by reading:
+//  * the label loop (copy_indexed: `i += nb * kBlock`, i < num_label) is the same cursor without a tail.  Same rule with
+//    rows = num_label, one chunk per row and a tile of kBlock (job_ok's num_label <= 2^32 - 1 is not enough by itself);
 //  * the segment copy (`i0 += U * stride`, stride = nb * kBlock) reads i = i0 + u * stride for u < U inside one step and
 //    guards each with `i >= i0`, so a wrapped i is dropped, not copied; the cursor i0 itself must not wrap either, which
 //    is the rule with rows = words, a tile of kBlock * U and the HBM band's workgroups.  The refusal of 2^31 words and
@@ -700,7 +691,7 @@ int fgnn::gather_rows_ex(void *out, const void *src, const uint32_t *src_index, 
                          const uint32_t *d_n, size_t n_cap, size_t dim, int dtype, uint32_t src_row_mask,
                          void *stream, const GatherTail *tail_in, size_t host_grid, size_t wg_per_cu_in) {
   auto s = static_cast<hipStream_t>(stream);
-  const GatherTail tail = tail_in ? *tail_in : GatherTail{nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, nullptr};
+  const GatherTail tail = tail_in ? *tail_in : GatherTail{};
   if (tail_in && !gather_takes_tail(out, src, d_n ? n_cap : n, dim, dtype)) return FGNN_EINVAL;
   const size_t esz = dtype_bytes(dtype);
   size_t cap = d_n ? n_cap : n;
@@ -746,23 +737,6 @@ int fgnn::gather_rows_ex(void *out, const void *src, const uint32_t *src_index, 
     // non-temporal stores too: 256 MB of gathered rows left as dirty lines in the Infinity Cache slow down the
     // cold random reads of the next batch's sampling chain (whole step 0.228 -> 0.207 ms)
     const bool nts = tune_int("FGNN_GATHER_NTS", 1) != 0;
-#define FGNN_GATHER3(U, C, N)                                                                                    \
-  do {                                                                                                           \
-    if (nts) hipLaunchKernelGGL((gather_rows16_kernel<U, C, N, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s, \
-                       static_cast<chunk16 *>(o), static_cast<const chunk16 *>(sp), si, di, nk, d_n, capk, cpr,  \
-                       src_row_mask, tail);                                                                      \
-    else hipLaunchKernelGGL((gather_rows16_kernel<U, C, N, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,  \
-                       static_cast<chunk16 *>(o), static_cast<const chunk16 *>(sp), si, di, nk, d_n, capk, cpr,  \
-                       src_row_mask, tail);                                                                      \
-  } while (0)
-#define FGNN_GATHER2(U, C) do { if (nt) FGNN_GATHER3(U, C, true); else FGNN_GATHER3(U, C, false); } while (0)
-#define FGNN_GATHER(U)                                  \
-  do {                                                  \
-    if (cpr == 32) FGNN_GATHER2(U, 32);                 \
-    else if (cpr == 64) FGNN_GATHER2(U, 64);            \
-    else if (cpr == 25) FGNN_GATHER2(U, 25);            \
-    else FGNN_GATHER2(U, 0);                            \
-  } while (0)
     for (size_t k = 0; k < plan.launches; ++k) {
       // (one launch: the caller's n, d_n and capacity as they are; slices are host-sized and carry no tail)
       const size_t r0 = plan.first_row(k), blocks = plan.grid(k);
@@ -770,31 +744,37 @@ int fgnn::gather_rows_ex(void *out, const void *src, const uint32_t *src_index, 
       void *o = dst_index ? out : static_cast<char *>(out) + r0 * row_bytes;
       const void *sp = src_index ? src : static_cast<const char *>(src) + r0 * row_bytes;
       const uint32_t *si = src_index ? src_index + r0 : nullptr, *di = dst_index ? dst_index + r0 : nullptr;
-      if (unroll == 8) FGNN_GATHER(8);
-      else if (unroll == 2) FGNN_GATHER(2);
-      else FGNN_GATHER(4);
+      pick_tuned<4, 2, 8>(unroll, [&](auto unroll_c) {
+        pick_cpr(cpr, [&](auto cpr_c) {
+          pick_tuned<true, false>(nt, [&](auto nt_c) {
+            pick_tuned<true, false>(nts, [&](auto nts_c) {
+              hipLaunchKernelGGL((gather_rows16_kernel<unroll_c(), cpr_c(), nt_c(), nts_c()>), dim3((unsigned)blocks),
+                                 dim3(kBlock), 0, s, static_cast<chunk16 *>(o), static_cast<const chunk16 *>(sp), si, di,
+                                 nk, d_n, capk, cpr, src_row_mask, tail);
+            });
+          });
+        });
+      });
       if (plan.launches > 1) {
         const int rc = launch_status(__func__);
         if (rc != FGNN_OK) return rc;
       }
     }
-#undef FGNN_GATHER
-#undef FGNN_GATHER2
-#undef FGNN_GATHER3
   } else {
     const size_t total = cap * dim;
     size_t blocks = div_up(total, kBlock);
     if (blocks > (size_t)device_cu_count() * 16) blocks = (size_t)device_cu_count() * 16;
-#define FGNN_ELEM(T)                                                                                              \
-  hipLaunchKernelGGL((gather_rows_elem_kernel<T>), dim3(blocks), dim3(kBlock), 0, s, static_cast<T *>(out),       \
-                     static_cast<const T *>(src), src_index, dst_index, n, d_n, cap, dim, src_row_mask)
+    auto launch = [&](auto elem) {
+      using T = decltype(elem);
+      hipLaunchKernelGGL((gather_rows_elem_kernel<T>), dim3(blocks), dim3(kBlock), 0, s, static_cast<T *>(out),
+                         static_cast<const T *>(src), src_index, dst_index, n, d_n, cap, dim, src_row_mask);
+    };
     switch (esz) {
-      case 1: FGNN_ELEM(uint8_t); break;
-      case 2: FGNN_ELEM(uint16_t); break;
-      case 4: FGNN_ELEM(uint32_t); break;
-      default: FGNN_ELEM(unsigned long long); break;
+      case 1: launch(uint8_t{}); break;
+      case 2: launch(uint16_t{}); break;
+      case 4: launch(uint32_t{}); break;
+      default: launch(0ull); break;
     }
-#undef FGNN_ELEM
   }
   return launch_status(__func__);
 }
@@ -867,8 +847,7 @@ int fgnn::extract_fused(const ExtractJob &j, void *stream, size_t *grid_out) {
   const size_t grid = p.link + p.hbm;
   if (grid_out) *grid_out = grid;
   if (grid == 0) return FGNN_OK;
-  FusedArgs a;
-  memset(static_cast<void *>(&a), 0, sizeof(a));
+  FusedArgs a{};
   a.out = static_cast<chunk16 *>(j.out);
   a.miss_rows = static_cast<const chunk16 *>(j.miss_rows);
   a.cache_rows = static_cast<const chunk16 *>(j.cache_rows);
@@ -890,22 +869,17 @@ int fgnn::extract_fused(const ExtractJob &j, void *stream, size_t *grid_out) {
     ++a.num_segs;
   }
   auto s = static_cast<hipStream_t>(stream);
-#define FGNN_FUSED2(UL, C) \
-  hipLaunchKernelGGL((extract_fused_kernel<UL, 4, C>), dim3((unsigned)grid), dim3(kBlock), 0, s, a)
-#define FGNN_FUSED(C) do { if (p.ul == 4) FGNN_FUSED2(4, C); else FGNN_FUSED2(8, C); } while (0)
-  if (p.cpr == 32) FGNN_FUSED(32);
-  else if (p.cpr == 64) FGNN_FUSED(64);
-  else if (p.cpr == 25) FGNN_FUSED(25);
-  else FGNN_FUSED(0);
-#undef FGNN_FUSED
-#undef FGNN_FUSED2
+  pick_tuned<4, 8>(p.ul, [&](auto ul_c) {
+    pick_cpr(p.cpr, [&](auto cpr_c) {
+      hipLaunchKernelGGL((extract_fused_kernel<ul_c(), 4, cpr_c()>), dim3((unsigned)grid), dim3(kBlock), 0, s, a);
+    });
+  });
   return launch_status(__func__);
 }
 
 namespace {
 ExtractJob job_from_c(const fgnn_extract_job *c) {
-  ExtractJob j;
-  memset(static_cast<void *>(&j), 0, sizeof(j));
+  ExtractJob j{};
   j.out = c->out;
   j.miss_rows = c->miss_rows; j.cache_rows = c->cache_rows;
   j.miss_src = c->miss_src; j.miss_dst = c->miss_dst; j.cache_src = c->cache_src; j.cache_dst = c->cache_dst;

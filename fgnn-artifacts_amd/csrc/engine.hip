@@ -793,8 +793,10 @@ namespace {
 // label rows + summary copy as a tail of the batch's last feature gather (cache_gather.hip), where that gather can carry one
 bool make_tail(fgnn_batch *b, const void *src, const void *label, fgnn::GatherTail *t) {
   if (!fgnn::gather_takes_tail(b->feat, src, b->feat_rows_cap, b->feat_dim, b->feat_dtype)) return false;
-  *t = fgnn::GatherTail{nullptr, nullptr, nullptr, 0, 0, reinterpret_cast<uint32_t *>(b->h_meta),
-                        reinterpret_cast<const uint32_t *>(b->d_meta), (uint32_t)(sizeof(fgnn_batch_meta) / 4), nullptr};
+  *t = fgnn::GatherTail{};
+  t->meta_dst = reinterpret_cast<uint32_t *>(b->h_meta);
+  t->meta_src = reinterpret_cast<const uint32_t *>(b->d_meta);
+  t->meta_words = (uint32_t)(sizeof(fgnn_batch_meta) / 4);
   if (label && b->num_output) {
     t->label_out = b->label;
     t->label_src = label;
@@ -869,8 +871,7 @@ extern "C" int fgnn_batch_extract_cached(fgnn_batch *b, const void *cache_rows, 
   // ONE launch (CombineMissData + CombineCacheData, cuda_cache_manager_device.cu:165-210,339-442,
   // with ExtractMissData's fetch fused in): a band of workgroups pulls the miss rows over the host link while the rest
   // of the grid streams the hit rows out of the HBM cache; labels and the summary ride in the HBM band
-  fgnn::ExtractJob job;
-  std::memset(static_cast<void *>(&job), 0, sizeof(job));
+  fgnn::ExtractJob job{};
   job.out = b->feat;
   job.miss_rows = full_feat;
   job.cache_rows = cache_rows;

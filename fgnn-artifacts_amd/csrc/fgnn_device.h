@@ -744,13 +744,13 @@ int hashtable_next_generation(fgnn_hashtable *ht, void *stream, bool zero_counts
 // small jobs of a batch that ride along with its feature gather launch (gather_rows16_kernel): the label rows of the
 // seeds and the copy of the batch summary into pinned host memory
 struct GatherTail {
-  void *label_out;              // null: no label job
-  const void *label_src;
-  const uint32_t *label_index;  // output_nodes
-  uint32_t num_label, label_esz;
-  uint32_t *meta_dst;           // null: no summary copy (else host-mapped, 4-byte words)
-  const uint32_t *meta_src;
-  uint32_t meta_words;          // <= 256
+  void *label_out = nullptr;              // null: no label job
+  const void *label_src = nullptr;
+  const uint32_t *label_index = nullptr;  // output_nodes
+  uint32_t num_label = 0, label_esz = 0;
+  uint32_t *meta_dst = nullptr;           // null: no summary copy (else host-mapped, 4-byte words)
+  const uint32_t *meta_src = nullptr;
+  uint32_t meta_words = 0;                // <= 256
   // null, or u64[2 * kGatherStampBlocks + 1] in pinned host memory: workgroup b posts its start / end clock (100 MHz) at
   // [2b], [2b + 1], workgroup 0 the grid size at [2 * kGatherStampBlocks] -- the launch's own duration without events
   unsigned long long *stamps = nullptr;
