@@ -89,6 +89,26 @@ def _fused_layers_apply(block, h):
             and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32)
 
 
+def _half_rows_apply(block, h):
+    """fp16 input features (the engine's `feat_store_dtype = f16`) that the first layer of the fused SAGE, GCN and
+    PinSAGE models reads as they are: the aggregation kernels upcast the rows on load (fgnn_block_aggregate_ex_f16 /
+    _scaled_f16, fgnn_sage_finish_z_f16), sums and everything behind them are fp32, and no fp32 copy of the num_src x D
+    feature tensor is written.  Input features take no gradient."""
+    return (_fused_aggregate is not None and h.is_cuda and h.dtype == th.float16 and not h.requires_grad
+            and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32)
+
+
+def input_rows(layer, block, x):
+    """what a model hands its first layer: x itself -- unless x is fp16 and the layer cannot read half rows (GAT, every
+    op-by-op layer, any layer off the GPU or without the HIP library): those get ONE torch upcast of the whole tensor,
+    num_src x D, which is what a half-precision store otherwise saves"""
+    if x.dtype != th.float16:
+        return x
+    if isinstance(layer, (FusedSAGEConv, FusedGraphConv, FusedWeightedSAGEConv)) and _half_rows_apply(block, x):
+        return x
+    return x.float()
+
+
 def _sum_to_dst(block, h, weight=None):
     num_dst = block.number_of_dst_nodes()
     if _fused_layers_apply(block, h):
@@ -134,7 +154,7 @@ class _FusedSageFn(th.autograd.Function):
         din = h.shape[1]
         # z and the in-degree counts out of ONE zeroed buffer (one fill), the neighbour sums and the counts by one
         # launch, the mean's scaling and the copy of the destinations' own rows by one more (fgnn_sage_finish_z)
-        buf = th.zeros(num_dst * (2 * din + 1), dtype=h.dtype, device=h.device)
+        buf = th.zeros(num_dst * (2 * din + 1), dtype=th.float32, device=h.device)  # (h may be fp16: upcast on load)
         z = buf[:num_dst * 2 * din].view(num_dst, 2 * din)
         deg = buf[num_dst * 2 * din:]
         aggregate_into(z[:, din:], h, block.row, block.col, in_degree=deg)
@@ -207,7 +227,7 @@ class FusedSAGEConv(nn.Module):
 
     def forward(self, block, h):
         num_dst = block.number_of_dst_nodes()
-        if _fused_layers_apply(block, h):
+        if _fused_layers_apply(block, h) or _half_rows_apply(block, h):
             return _FusedSageFn.apply(h, self.weight, self.bias, block, num_dst)
         agg = _sum_to_dst(block, h) / _in_degree(block, h.dtype).clamp(min=1).unsqueeze(1)
         return th.cat([h[:num_dst], agg], 1).mm(self.weight.t()) + self.bias
@@ -270,7 +290,7 @@ class _FusedGraphConvFn(th.autograd.Function):
         from fgnn_hip.nn import aggregate_scaled_into, block_degrees
         h = h.contiguous()
         src_deg, dst_deg = block_degrees(block.row, block.col, h.shape[0], num_dst)
-        agg = th.zeros((num_dst, h.shape[1]), dtype=h.dtype, device=h.device)
+        agg = th.zeros((num_dst, h.shape[1]), dtype=th.float32, device=h.device)  # (h may be fp16: upcast on load)
         aggregate_scaled_into(agg, h, block.row, block.col, None, src_deg, 1, dst_deg, 1)
         ctx.save_for_backward(agg, weight, block.row, block.col, src_deg, dst_deg)
         ctx.num_src = h.shape[0]
@@ -297,7 +317,7 @@ class FusedGraphConv(GraphConv):
     it IS GraphConv."""
 
     def conv(self, block, h):
-        if _fused_layers_apply(block, h):
+        if _fused_layers_apply(block, h) or _half_rows_apply(block, h):
             return _FusedGraphConvFn.apply(h, self.fc.weight, self.fc.bias, block, block.number_of_dst_nodes())
         return super().conv(block, h)
 
@@ -317,7 +337,7 @@ class _WeightedMeanCatFn(th.autograd.Function):
         z[:, :hidden] = 0
         aggregate_scaled_into(z[:, :hidden], q if q.stride(1) == 1 else q.contiguous(), block.row, block.col, w,
                               dst_deg=ws, dst_mode=2)
-        z[:, hidden:] = h[:num_dst]
+        z[:, hidden:] = h[:num_dst]  # (fp16 input features: only these num_dst rows are upcast)
         ctx.save_for_backward(block.row, block.col, w, ws)
         ctx.shape = (q.shape[0], h.shape[0], hidden, din)
         return z
@@ -343,14 +363,16 @@ class FusedWeightedSAGEConv(WeightedSAGEConv):
     """WeightedSAGEConv on the fused kernels: the weighted mean lands in its half of the concatenation in one launch
     (_WeightedMeanCatFn), ReLU + row normalisation are one launch each way (fgnn_relu_l2norm); the GEMMs and the two
     dropouts stay torch ops.  Same parameters under the same names (Q.*, W.*); off the GPU / without the HIP library /
-    for other dtypes it IS WeightedSAGEConv."""
+    for other dtypes it IS WeightedSAGEConv.  fp16 input features: what this layer aggregates is q = relu(Q h), so
+    the Q GEMM still needs fp32 operands (half-precision GEMMs are not built) and upcasts h for itself; the
+    destinations' own rows go from the fp16 tensor straight into the concatenation."""
 
     def forward(self, block, h):
-        if not _fused_layers_apply(block, h):
+        if not (_fused_layers_apply(block, h) or _half_rows_apply(block, h)):
             return super().forward(block, h)
         from fgnn_hip.nn import relu_l2norm
-        w = block.edata["weights"].to(h.dtype)
-        q = F.relu(self.Q(self.dropout(h)))
+        w = block.edata["weights"].to(th.float32)
+        q = F.relu(self.Q(self.dropout(h.float())))  # (.float() of an fp32 tensor is the tensor itself)
         z = _WeightedMeanCatFn.apply(q, h, block, w.contiguous(), block.number_of_dst_nodes())
         return relu_l2norm(self.W(self.dropout(z)))
 
@@ -478,7 +500,7 @@ class GAT(nn.Module):
         if self.fused and self.dropout_step is None and self.training:
             self._host_draws += 1
             seed = (seed + 0x9E3779B97F4A7C15 * self._host_draws) & 0xFFFFFFFFFFFFFFFF
-        h = x
+        h = input_rows(self.layers[0], blocks[0], x)  # fp16 features: GAT upcasts once with torch
         for i, (layer, block) in enumerate(zip(self.layers, blocks)):
             if self.fused:
                 layer.dropout_key = (seed, self.dropout_step, i)
@@ -501,7 +523,7 @@ class SAGE(nn.Module):
         self.dropout_seed = 0x5A4D47
 
     def forward(self, blocks, x):
-        h = x
+        h = input_rows(self.layers[0], blocks[0], x)
         for l, (layer, block) in enumerate(zip(self.layers, blocks)):
             h = layer(block, h)
             if l != len(self.layers) - 1:
@@ -529,7 +551,7 @@ class GCN(nn.Module):
         self.dropout_seed = 0x5A4D47
 
     def forward(self, blocks, x):
-        h = x
+        h = input_rows(self.layers[0], blocks[0], x)
         if self.fused and self.dropout_step is not None:
             from fgnn_hip.nn import relu_dropout
             for i, (layer, block) in enumerate(zip(self.layers, blocks)):
@@ -557,7 +579,7 @@ class PinSAGE(nn.Module):
         self.layers = nn.ModuleList(conv(dims[i], n_hidden, dims[i + 1], dropout) for i in range(n_layers))
 
     def forward(self, blocks, x):
-        h = x
+        h = input_rows(self.layers[0], blocks[0], x)
         for layer, block in zip(self.layers, blocks):
             h = layer(block, h)
         return h

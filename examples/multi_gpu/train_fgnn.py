@@ -55,6 +55,10 @@ def build_parser():
     ap.add_argument("--num-train-worker", type=int, default=1)
     ap.add_argument("--single-gpu", action="store_true", help="all workers on cuda:0 (common_config.py:186-191)")
     ap.add_argument("--cache-policy", default="pre_sample", choices=list(sam.cache_policies))
+    ap.add_argument("--feat-store", default="f32", choices=["f32", "f16"],
+                    help="f16: the engine keeps, caches and gathers the input features as IEEE binary16 rows "
+                         "(config key feat_store_dtype; feat_f16.bin, written by --make-dataset or by `fgnn_dataset "
+                         "feat-f16`) and the fused models' first layer reads them as they are; compute stays fp32")
     ap.add_argument("--cache-percentage", type=float, default=0.0)
     ap.add_argument("--no-pipeline", action="store_true")
     ap.add_argument("--async", dest="async_train", action="store_true",
@@ -92,6 +96,8 @@ def get_run_config(args):
         fan = args.fanout or ([25, 10] if args.model == "graphsage" else [5, 10, 15])
         rc.update(num_fanout=len(fan), fanout=fan, num_layer=len(fan))
     rc["_sample_type"] = sam.sample_types[st]
+    if args.feat_store != "f32":  # (the key is optional: without it the engine's run is the fp32 one, byte for byte)
+        rc["feat_store_dtype"] = args.feat_store
     n_dev = torch.cuda.device_count()
     ns, nt = args.num_sample_worker, args.num_train_worker
     if args.single_gpu or n_dev < ns + nt:
@@ -238,7 +244,7 @@ def make_dataset(args):
         root, name = os.path.split(args.dataset_path.rstrip("/"))
         synth.write_dataset(root, name, shape["num_node"], shape["num_edge"], shape["feat_dim"], shape["num_class"],
                             shape["num_train"], shape.get("num_valid", 1000), shape.get("num_test", 1000),
-                            learnable=args.make_dataset == "learnable",
+                            learnable=args.make_dataset == "learnable", feat_f16=args.feat_store == "f16",
                             with_prefix=args.sample_type == "weighted_khop_prefix",
                             with_alias=args.sample_type in ("weighted_khop", "weighted_khop_hash_dedup"))
 

@@ -65,6 +65,10 @@ def main():
     # GAT (example/samgraph/train_gat.py: 8 heads x 32 hidden, attention dropout = feature dropout)
     ap.add_argument("--num-heads", type=int, default=8, help="gat: attention heads of the inner layers")
     ap.add_argument("--attn-drop", type=float, default=None, help="gat: attention dropout (default: --dropout)")
+    ap.add_argument("--feat-store", default="f32", choices=["f32", "f16"],
+                    help="f16: the engine keeps, caches and gathers the input features as IEEE binary16 rows "
+                         "(config key feat_store_dtype; feat_f16.bin, written by --make-dataset or by `fgnn_dataset "
+                         "feat-f16`) and the fused models' first layer reads them as they are; compute stays fp32")
     ap.add_argument("--cache-policy", default="pre_sample",
                     help="a key of sam.cache_policies: pre_sample, presample_static, degree, ..., or dynamic_cache "
                          "(arch4 only: the cache is the previous batch's feature tensor; khop0 / khop1 / weighted_khop, "
@@ -80,7 +84,7 @@ def main():
         t0 = time.time()
         synth.write_dataset(root, name, shape["num_node"], shape["num_edge"], shape["feat_dim"], shape["num_class"],
                             shape["num_train"], shape.get("num_valid", 1000), shape.get("num_test", 1000),
-                            learnable=args.make_dataset == "learnable")
+                            learnable=args.make_dataset == "learnable", feat_f16=args.feat_store == "f16")
         print("dataset written in {:.1f}s".format(time.time() - t0))
 
     two = th.cuda.device_count() >= 2
@@ -100,6 +104,8 @@ def main():
                           num_neighbor=args.num_neighbor, num_layer=args.num_layer)
     else:
         run_config.update(num_fanout=len(args.fanout), fanout=args.fanout)
+    if args.feat_store != "f32":  # (the key is optional: without it the engine's run is the fp32 one, byte for byte)
+        run_config["feat_store_dtype"] = args.feat_store
     sam.config(run_config)
     sam.init()
     pipeline = args.pipeline and arch != "arch1"  # arch1 doesn't support pipelining (common_config.py:212-214)

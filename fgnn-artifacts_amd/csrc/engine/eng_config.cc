@@ -107,6 +107,11 @@ void RunConfig::Parse(const char **keys, const char **vals, size_t n) {
   SAM_CHECK(!fanout.empty() && fanout.size() <= FGNN_MAX_LAYERS);
   barriered_epoch = raw.count("barriered_epoch") ? std::stoi(raw["barriered_epoch"]) : 0;
   presample_epoch = raw.count("presample_epoch") ? std::stoi(raw["presample_epoch"]) : 0;
+  if (raw.count("feat_store_dtype")) {
+    const std::string &v = raw["feat_store_dtype"];
+    SAM_CHECK(v == "f32" || v == "f16") << "bad config value feat_store_dtype = " << v << " (f32 or f16)";
+    feat_store_f16 = v == "f16";
+  }
   if (raw.count("seed")) seed = std::stoull(raw["seed"], nullptr, 0);
   // environment
   if (const char *e = getenv("SAMGRAPH_PROFILE_LEVEL")) profile_level = atoi(e);

@@ -32,6 +32,9 @@ struct RunConfig {
   size_t worker_id = 0, num_worker = 1;  // arch6 (num_worker), arch7 (both)
   bool have_switcher = false;
   int barriered_epoch = 0, presample_epoch = 0;
+  // feat_store_dtype (optional: f32, the default, or f16): the input features are stored, cached, gathered and handed
+  // to the trainer as IEEE binary16 rows from feat_f16.bin -- half the bytes at every step that moves them
+  bool feat_store_f16 = false;
   int omp_thread_num = 1;
   uint64_t seed = 0x5A4D47;
   bool is_configured = false;

@@ -248,9 +248,18 @@ void Dataset::Load(const RunConfig &rc) {
 
   // features: file, or an uninitialised buffer (engine.cc:138-155); SAMGRAPH_EMPTY_FEAT=k => 2^k rows
   feat_rows = rc.option_empty_feat ? (1ull << rc.option_empty_feat) : num_node;
-  if (!rc.option_empty_feat) feat = ReadFileShared(dir + "feat.bin", num_node * feat_dim * 4, true);
+  feat_dtype = rc.feat_store_f16 ? FGNN_F16 : FGNN_F32;
+  feat_esz = rc.feat_store_f16 ? 2 : 4;
+  if (!rc.option_empty_feat) {
+    feat = ReadFileShared(dir + (rc.feat_store_f16 ? "feat_f16.bin" : "feat.bin"), num_node * feat_dim * feat_esz, true);
+    // (a missing feat.bin is the reference's uninitialised buffer; a missing half-precision table is a run that was
+    // asked for something nobody prepared)
+    SAM_CHECK(feat.ptr || !rc.feat_store_f16)
+        << "feat_store_dtype = f16 but " << dir << "feat_f16.bin is absent: write it with `fgnn_dataset feat-f16 " << dir
+        << "`";
+  }
   if (!feat.ptr) {
-    feat.bytes = feat_rows * feat_dim * 4;
+    feat.bytes = feat_rows * feat_dim * feat_esz;
     SharedRegion reg = SharedCreate(feat.bytes);
     feat.ptr = reg.ptr;
     if (reg.creator) {

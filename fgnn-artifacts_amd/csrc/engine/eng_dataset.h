@@ -21,6 +21,10 @@ struct Dataset {
       ranking_file;
   uint32_t *ranking_nodes = nullptr;  // shared anonymous mapping for pre_sample, or the ranking file
   size_t feat_rows = 0;               // num_node, or 2^SAMGRAPH_EMPTY_FEAT
+  // the feature table's element type and size, by the config key feat_store_dtype: FGNN_F32 / 4 (feat.bin), or
+  // FGNN_F16 / 2 (feat_f16.bin, written by `fgnn_dataset feat-f16`); every gather, cache and batch buffer follows them
+  int feat_dtype = FGNN_F32;
+  size_t feat_esz = 4;
   void Load(const RunConfig &rc);
 };
 

@@ -233,14 +233,14 @@ void Engine::SampleOnceDynamic() {
   const uint32_t *t_idx[4] = {to_trainer(idx[0], num_miss * 4), to_trainer(idx[1], num_miss * 4),
                               to_trainer(idx[2], num_cache * 4), to_trainer(idx[3], num_cache * 4)};
   const uint32_t *t_out = to_trainer(out_nodes.get(), bsize * sizeof(uint32_t));
-  const size_t row_bytes = ds_.feat_dim * 4;
+  const size_t row_bytes = ds_.feat_dim * ds_.feat_esz;
   auto feat = Pooled(dev_pool_, num_all * row_bytes);
   if (num_miss)   // ExtractMissData + copy + CombineMissData (:1222-1251), the host fetch done by the gather itself
     SAM_FGNN(fgnn_gather_rows_masked(feat.get(), dev_host_feat_, t_idx[0], t_idx[1], num_miss, nullptr, num_miss,
-                                     ds_.feat_dim, FGNN_F32, FeatRowMask(), tstream_));
+                                     ds_.feat_dim, ds_.feat_dtype, FeatRowMask(), tstream_));
   if (num_cache)  // CombineCacheData (:1253-1259): rows of the previous batch's tensor
     SAM_FGNN(fgnn_gather_rows(feat.get(), dc.prev_feat.get(), t_idx[2], t_idx[3], num_cache, nullptr, num_cache,
-                              ds_.feat_dim, FGNN_F32, tstream_));
+                              ds_.feat_dim, ds_.feat_dtype, tstream_));
   auto lab = Pooled(dev_pool_, bsize * 8);
   SAM_FGNN(fgnn_gather_rows(lab.get(), d_label_, t_out, nullptr, bsize, nullptr, std::max<size_t>(bsize, 1), 1, FGNN_I64,
                             tstream_));

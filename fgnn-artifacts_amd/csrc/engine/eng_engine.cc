@@ -147,7 +147,7 @@ void Engine::CreateSamplerSlots(size_t streams, size_t slots) {
   for (size_t i = 0; i < slots_.size(); ++i) {
     Slot &s = slots_[i];
     int err = 0;
-    s.fb = fgnn_batch_create(sampler_, 0, FGNN_F32, FGNN_I64, 0, &err);
+    s.fb = fgnn_batch_create(sampler_, 0, ds_.feat_dtype, FGNN_I64, 0, &err);
     SAM_CHECK(s.fb) << "fgnn_batch_create failed: " << err << " " << fgnn_last_error();
     if (i < n_streams) {
       SAM_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
@@ -254,7 +254,7 @@ void Engine::InitSingleGPU(bool extract) {
   slots_.resize(RC().max_copying_jobs + 2);
   for (auto &s : slots_) {
     int err = 0;
-    s.fb = fgnn_batch_create(sampler_, extract ? ds_.feat_dim : 0, FGNN_F32, FGNN_I64, 0, &err);
+    s.fb = fgnn_batch_create(sampler_, extract ? ds_.feat_dim : 0, ds_.feat_dtype, FGNN_I64, 0, &err);
     SAM_CHECK(s.fb) << "fgnn_batch_create failed: " << err << " " << fgnn_last_error();
     if (extract) SAM_FGNN(fgnn_batch_set_feat_row_mask(s.fb, FeatRowMask()));
     SAM_HIP(hipEventCreate(&s.e0));
@@ -392,7 +392,7 @@ void Engine::SampleOnceArch1() {
   P.LogStep(key, kLogL2CoreSampleTime, ms_sample * 1e-3);
   P.LogStep(key, kLogL2ExtractTime, ms_extract * 1e-3);
   if (extract) {
-    P.LogStep(key, kLogL1FeatureBytes, (double)m.num_input * ds_.feat_dim * 4);
+    P.LogStep(key, kLogL1FeatureBytes, (double)m.num_input * ds_.feat_dim * ds_.feat_esz);
     P.LogStep(key, kLogL1LabelBytes, (double)m.num_output * 8);
   }
   P.LogEpochAdd(key, kLogEpochSampleTime, shuffle_time + ms_sample * 1e-3);
@@ -778,14 +778,14 @@ void Engine::TrainInit(int worker_id, Context ctx, DistType type) {
 void Engine::BuildTrainerCache() {
   // DistCacheManager (dist_cache_manager_host.cc:60-119): top cache_percentage*N rows of the ranking
   num_cached_ = (size_t)(ds_.num_node * RC().cache_percentage);
-  const size_t row_bytes = ds_.feat_dim * 4;
+  const size_t row_bytes = ds_.feat_dim * ds_.feat_esz;
   SAM_HIP(hipMalloc(&d_cache_rows_, num_cached_ ? num_cached_ * row_bytes : 16));
   if (num_cached_) {
     uint32_t *d_rank = nullptr;
     SAM_HIP(hipMalloc(&d_rank, num_cached_ * sizeof(uint32_t)));
     SAM_HIP(hipMemcpy(d_rank, ds_.ranking_nodes, num_cached_ * sizeof(uint32_t), hipMemcpyHostToDevice));
     SAM_FGNN(fgnn_gather_rows_masked(d_cache_rows_, dev_host_feat_, d_rank, nullptr, num_cached_, nullptr, num_cached_,
-                                     ds_.feat_dim, FGNN_F32, FeatRowMask(), tstream_));
+                                     ds_.feat_dim, ds_.feat_dtype, FeatRowMask(), tstream_));
     SAM_HIP(hipStreamSynchronize(tstream_));
     (void)hipFree(d_rank);
   }
@@ -974,7 +974,7 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
                         << "mapped slot differs from what the sampler packed";
   }
   // features (DoCacheFeatureCopy / DoSwitchCacheFeatureCopy / DoCPUFeatureExtract+DoFeatureCopy)
-  const size_t row_bytes = ds_.feat_dim * 4;
+  const size_t row_bytes = ds_.feat_dim * ds_.feat_esz;
   void *d_feat = dev_pool_.Alloc(hdr.input_size * row_bytes);
   b->pooled.push_back(d_feat);
   b->feat = d_feat;
@@ -1002,7 +1002,7 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
     j.num_miss = num_miss;
     j.num_cache = num_cache;
     j.dim = ds_.feat_dim;
-    j.dtype = FGNN_F32;
+    j.dtype = ds_.feat_dtype;
     j.miss_row_mask = FeatRowMask();
     j.label_out = d_lab;
     j.label_src = d_label_;
@@ -1034,7 +1034,7 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
     // everything went with the one launch above
   } else if (!use_cache) {
     SAM_FGNN(fgnn_gather_rows_shared(d_feat, dev_host_feat_, d_input, nullptr, hdr.input_size, nullptr, hdr.input_size,
-                                     ds_.feat_dim, FGNN_F32, FeatRowMask(), ExtractorSharesGpu(), tstream_));
+                                     ds_.feat_dim, ds_.feat_dtype, FeatRowMask(), ExtractorSharesGpu(), tstream_));
     miss_rows = hdr.input_size;
   } else if (dist_type_ == DistType::Switch) {
     // own (smaller) cache: split on this GPU with device-side counts
@@ -1056,15 +1056,15 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
     j.d_counts = d_counts;
     j.cap = n;
     j.dim = ds_.feat_dim;
-    j.dtype = FGNN_F32;
+    j.dtype = ds_.feat_dtype;
     j.miss_row_mask = FeatRowMask();
     j.link_workgroups = FGNN_LINK_WGS_SHARED;  // a switcher shares its GPU with a sampler
     if (fgnn_extract_fused_grid(&j)) {
       SAM_FGNN(fgnn_extract_fused(&j, tstream_));
     } else {
-      SAM_FGNN(fgnn_gather_rows_shared(d_feat, dev_host_feat_, idx[0], idx[1], 0, d_counts, n, ds_.feat_dim, FGNN_F32,
+      SAM_FGNN(fgnn_gather_rows_shared(d_feat, dev_host_feat_, idx[0], idx[1], 0, d_counts, n, ds_.feat_dim, ds_.feat_dtype,
                                        FeatRowMask(), ExtractorSharesGpu(), tstream_));
-      SAM_FGNN(fgnn_gather_rows(d_feat, d_cache_rows_, idx[2], idx[3], 0, d_counts + 1, n, ds_.feat_dim, FGNN_F32,
+      SAM_FGNN(fgnn_gather_rows(d_feat, d_cache_rows_, idx[2], idx[3], 0, d_counts + 1, n, ds_.feat_dim, ds_.feat_dtype,
                                 tstream_));
     }
   } else {
@@ -1072,11 +1072,11 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
     SAM_HIP(hipEventRecord(te_[0], tstream_));
     if (num_miss)   // CombineMissData with the host fetch fused in
       SAM_FGNN(fgnn_gather_rows_shared(d_feat, dev_host_feat_, d_cidx[0], d_cidx[1], num_miss, nullptr, num_miss,
-                                       ds_.feat_dim, FGNN_F32, FeatRowMask(), ExtractorSharesGpu(), tstream_));
+                                       ds_.feat_dim, ds_.feat_dtype, FeatRowMask(), ExtractorSharesGpu(), tstream_));
     SAM_HIP(hipEventRecord(te_[1], tstream_));
     if (num_cache)  // CombineCacheData
       SAM_FGNN(fgnn_gather_rows(d_feat, d_cache_rows_, d_cidx[2], d_cidx[3], num_cache, nullptr, num_cache,
-                                ds_.feat_dim, FGNN_F32, tstream_));
+                                ds_.feat_dim, ds_.feat_dtype, tstream_));
     SAM_HIP(hipEventRecord(te_[2], tstream_));
     timed_gathers = true;
   }
@@ -1105,7 +1105,7 @@ void Engine::TrainerComplete(ExtractCtx &x) {
   const double recv_time = x.recv_time;
   const Timer &t_copy = x.t_copy;
   const bool timed_gathers = x.timed_gathers;
-  const size_t row_bytes = ds_.feat_dim * 4;
+  const size_t row_bytes = ds_.feat_dim * ds_.feat_esz;
   struct { size_t input_size, output_size; } hdr{x.input_size, x.output_size};
   Timer t_wait;
   while (pool_->Full() && !shutdown_) std::this_thread::sleep_for(std::chrono::microseconds(1));

@@ -290,3 +290,15 @@ extern "C" int fgnn_host_config_probe(const char **keys, const char **vals, size
   out[3] = rc.UseGPUCache() ? 1 : 0;
   return 0;
 }
+
+extern "C" int fgnn_host_feat_store_probe(const char **keys, const char **vals, size_t n, size_t out[4]) {
+  RunConfig rc;
+  rc.Parse(keys, vals, n);
+  Dataset ds;
+  ds.Load(rc);
+  out[0] = (size_t)ds.feat_dtype;
+  out[1] = ds.feat_esz;
+  out[2] = ds.feat.bytes;
+  out[3] = ds.feat.from_file ? 1 : 0;
+  return 0;
+}

@@ -184,7 +184,7 @@ const void *samgraph_torch_get_graph_feat_ptr(uint64_t key, size_t *num_rows, si
   auto b = CurrentChecked(key);
   *num_rows = b->feat_rows;
   *dim = Engine::Get().Data().feat_dim;
-  *dtype = FGNN_F32;
+  *dtype = Engine::Get().Data().feat_dtype;
   *device = b->device;
   return b->feat;
 }
@@ -232,7 +232,7 @@ const void *samgraph_torch_get_dataset_feat_ptr(size_t *num_rows, size_t *dim, i
   auto &d = Engine::Get().Data();
   *num_rows = d.feat_rows;
   *dim = d.feat_dim;
-  *dtype = FGNN_F32;
+  *dtype = d.feat_dtype;
   return d.feat.ptr;
 }
 const void *samgraph_torch_get_dataset_label_ptr(size_t *num, int *dtype) {

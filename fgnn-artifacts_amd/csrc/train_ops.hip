@@ -11,20 +11,31 @@
 //   fgnn_relu_dropout       F.relu + nn.Dropout (forward: Philox mask from a device-side step counter; backward from y)
 //   fgnn_softmax_xent       log_softmax + nll_loss(mean) forward AND the gradient of the logits, deterministic sum
 //   fgnn_adam_step          torch.optim.Adam's update for up to 8 tensors in one launch, step count on the device
+#include <hip/hip_fp16.h>
+
 #include "fgnn_device.h"
 
 namespace fgnn {
 namespace {
 
+typedef float f4 __attribute__((ext_vector_type(4)));
+// four adjacent columns of a row of h as fp32: one 16-byte load, or one 8-byte load of binary16 values + exact upcasts
+__device__ __forceinline__ f4 load4(const float *p) { return *reinterpret_cast<const f4 *>(p); }
+__device__ __forceinline__ f4 load4(const __half *p) {
+  const __half2 lo = reinterpret_cast<const __half2 *>(p)[0], hi = reinterpret_cast<const __half2 *>(p)[1];
+  return f4{__low2float(lo), __high2float(lo), __low2float(hi), __high2float(hi)};
+}
+
 // z[:, :din] = h[:num_dst], z[:, din:] *= inv, inv = 1 / max(deg, 1) (also stored: the backward pass scales with it)
+// H: the element type of h (float, or __half for the first layer over a half-precision feature store)
+template <typename H>
 __global__ __launch_bounds__(kBlock) void sage_finish_z_kernel(float *__restrict__ z, uint32_t ld,
-                                                               const float *__restrict__ h, uint32_t h_ld,
+                                                               const H *__restrict__ h, uint32_t h_ld,
                                                                const float *__restrict__ deg, float *__restrict__ inv_out,
                                                                uint32_t num_dst, uint32_t din) {
   // one thread per (row, 4 columns of the left half and the matching 4 of the right half)
   const uint32_t q = din / 4;
   const size_t total = (size_t)num_dst * q;
-  typedef float f4 __attribute__((ext_vector_type(4)));
   for (size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += (size_t)gridDim.x * kBlock) {
     const uint32_t i = (uint32_t)(t / q), c = (uint32_t)(t - (size_t)i * q) * 4;
     const float d = deg[i];
@@ -32,7 +43,7 @@ __global__ __launch_bounds__(kBlock) void sage_finish_z_kernel(float *__restrict
     if (c == 0) inv_out[i] = inv;
     f4 *zl = reinterpret_cast<f4 *>(z + (size_t)i * ld + c);
     f4 *zr = reinterpret_cast<f4 *>(z + (size_t)i * ld + din + c);
-    *zl = *reinterpret_cast<const f4 *>(h + (size_t)i * h_ld + c);
+    *zl = load4(h + (size_t)i * h_ld + c);
     f4 v = *zr;
     v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
     *zr = v;
@@ -266,21 +277,33 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(AdamTensors t, float lr, f
 
 using namespace fgnn;
 
-extern "C" int fgnn_sage_finish_z(float *z, size_t ld, const float *h, size_t h_ld, const float *deg, float *inv,
-                                  size_t num_dst, size_t din, void *stream) {
+// fgnn_sage_finish_z and its fp16-h twin: the checks and the launch (rows of h: 4 elements = one vector load apart)
+template <typename H>
+static int launch_sage_finish_z(const char *what, float *z, size_t ld, const H *h, size_t h_ld, const float *deg,
+                                float *inv, size_t num_dst, size_t din, void *stream) {
   if (num_dst == 0) return FGNN_OK;
   if (!z || !h || !deg || !inv || din == 0 || din % 4 || ld < 2 * din || ld % 4 || h_ld < din || h_ld % 4 ||
       num_dst > 0xffffffffull || ld > 0xffffffffull || h_ld > 0xffffffffull ||
-      reinterpret_cast<uintptr_t>(z) % 16 || reinterpret_cast<uintptr_t>(h) % 16)
+      reinterpret_cast<uintptr_t>(z) % 16 || reinterpret_cast<uintptr_t>(h) % (4 * sizeof(H)))
     return FGNN_EINVAL;
   auto st = static_cast<hipStream_t>(stream);
   const size_t total = num_dst * (din / 4);
   size_t blocks = div_up(total, (size_t)kBlock);
   const size_t most = (size_t)device_cu_count() * 16;
   if (blocks > most) blocks = most;
-  hipLaunchKernelGGL(sage_finish_z_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, z, (uint32_t)ld, h,
+  hipLaunchKernelGGL(sage_finish_z_kernel<H>, dim3((unsigned)blocks), dim3(kBlock), 0, st, z, (uint32_t)ld, h,
                      (uint32_t)h_ld, deg, inv, (uint32_t)num_dst, (uint32_t)din);
-  return launch_status(__func__);
+  return launch_status(what);
+}
+
+extern "C" int fgnn_sage_finish_z(float *z, size_t ld, const float *h, size_t h_ld, const float *deg, float *inv,
+                                  size_t num_dst, size_t din, void *stream) {
+  return launch_sage_finish_z(__func__, z, ld, h, h_ld, deg, inv, num_dst, din, stream);
+}
+
+extern "C" int fgnn_sage_finish_z_f16(float *z, size_t ld, const void *h, size_t h_ld, const float *deg, float *inv,
+                                      size_t num_dst, size_t din, void *stream) {
+  return launch_sage_finish_z(__func__, z, ld, static_cast<const __half *>(h), h_ld, deg, inv, num_dst, din, stream);
 }
 
 extern "C" int fgnn_sage_grad_prep(const float *gz, size_t gz_ld, const float *inv, float *gh, float *gagg,

@@ -104,6 +104,8 @@ SIGNATURES = {
     "fgnn_block_aggregate_ex": (_I, (_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P)),
     "fgnn_block_degrees": (_I, (_P, _P, _P, _Z, _P, _P, _P)),
     "fgnn_block_aggregate_scaled": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P)),
+    "fgnn_block_aggregate_ex_f16": (_I, (_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P)),
+    "fgnn_block_aggregate_scaled_f16": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P)),
     "fgnn_relu_l2norm": (_I, (_P, _Z, _P, _Z, _P, _Z, _Z, _P)),
     "fgnn_relu_l2norm_backward": (_I, (_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P)),
     "fgnn_gat_workspace_bytes": (_Z, (_Z, _Z, _Z)),
@@ -111,6 +113,7 @@ SIGNATURES = {
     "fgnn_gat_backward": (_I, (_P, _P, _Z, _P, _P, _P, _Z, _P, _P, _Z, _Z, _Z, _Z, _F, _F, _U64, _P, _U32, _P, _Z, _P,
                              _P, _P, _Z, _P)),
     "fgnn_sage_finish_z": (_I, (_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P)),
+    "fgnn_sage_finish_z_f16": (_I, (_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P)),
     "fgnn_sage_grad_prep": (_I, (_P, _Z, _P, _P, _P, _Z, _Z, _Z, _P)),
     "fgnn_relu_dropout": (_I, (_P, _P, _Z, _F, _U64, _P, _U32, _P)),
     "fgnn_relu_dropout_backward": (_I, (_P, _P, _P, _Z, _F, _P)),

@@ -16,19 +16,20 @@ _ptr, _st = _lib._ptr, _lib._stream
 def _aggregate(out, h, src_idx, dst_idx, weight, in_degree=None, scaling=None):
     """the one aggregation call: out[dst_idx[e]] += weight[e] * h[src_idx[e]] through fgnn_block_aggregate_ex (h
     contiguous; in_degree optional), or, with scaling = (src_deg, src_mode, dst_deg, dst_mode), through
-    fgnn_block_aggregate_scaled (h with a row stride, degree factors inside)"""
+    fgnn_block_aggregate_scaled (h with a row stride, degree factors inside).  h float16 (input features of a
+    half-precision store): the _f16 twin of either, which upcasts the rows on load."""
     L = _lib.load()
     n, dim = src_idx.numel(), h.shape[1]
+    f16 = "_f16" if h.dtype == torch.float16 else ""
     if scaling is None:
-        code = L.fgnn_block_aggregate_ex(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, _ptr(h), dim, _ptr(out),
-                                         out.stride(0), _ptr(in_degree), _st(h))
-        what = "fgnn_block_aggregate_ex"
+        what = "fgnn_block_aggregate_ex" + f16
+        code = getattr(L, what)(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, _ptr(h), dim, _ptr(out),
+                                out.stride(0), _ptr(in_degree), _st(h))
     else:
         src_deg, src_mode, dst_deg, dst_mode = scaling
-        code = L.fgnn_block_aggregate_scaled(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, _ptr(h), h.stride(0), dim,
-                                             _ptr(out), out.stride(0), _ptr(src_deg), src_mode, _ptr(dst_deg), dst_mode,
-                                             _st(h))
-        what = "fgnn_block_aggregate_scaled"
+        what = "fgnn_block_aggregate_scaled" + f16
+        code = getattr(L, what)(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, _ptr(h), h.stride(0), dim, _ptr(out),
+                                out.stride(0), _ptr(src_deg), src_mode, _ptr(dst_deg), dst_mode, _st(h))
     _lib._check(code, what)
     return out
 
@@ -56,8 +57,10 @@ class _BlockAggregate(torch.autograd.Function):
 
 
 def block_aggregate(h, row, col, num_dst, edge_weight=None):
-    """sum_e edge_weight[e] * h[row[e]] into out[col[e]]; h float32 [num_src, D], row / col int32 [E]."""
-    assert h.dtype == torch.float32 and row.dtype == torch.int32 and col.dtype == torch.int32
+    """sum_e edge_weight[e] * h[row[e]] into out[col[e]] (fp32); h float32 [num_src, D] -- or float16 where it needs no
+    gradient (input features of a half-precision store) --, row / col int32 [E]."""
+    assert h.dtype == torch.float32 or (h.dtype == torch.float16 and not h.requires_grad)
+    assert row.dtype == torch.int32 and col.dtype == torch.int32
     assert row.is_contiguous() and col.is_contiguous() and row.numel() == col.numel()
     if edge_weight is not None:
         edge_weight = edge_weight.to(torch.float32).contiguous()
@@ -68,8 +71,8 @@ def aggregate_into(out, h, src_idx, dst_idx, edge_weight=None, in_degree=None):
     """out[dst_idx[e]] += edge_weight[e] * h[src_idx[e]] into a caller-initialised fp32 tensor: no autograd, for layers
     that write their own backward (examples/models.py: FusedSAGEConv).  `out` may be a column block of a wider
     row-major matrix (unit stride inside a row); in_degree (fp32 [num_dst], caller-zeroed) receives the edge count of
-    every destination on the way."""
-    assert h.dtype == torch.float32 and out.dtype == torch.float32 and h.is_contiguous()
+    every destination on the way.  h: fp32, or fp16 rows that are upcast on load."""
+    assert h.dtype in (torch.float32, torch.float16) and out.dtype == torch.float32 and h.is_contiguous()
     assert out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
     assert src_idx.dtype == torch.int32 and dst_idx.dtype == torch.int32
     return _aggregate(out, h, src_idx, dst_idx, edge_weight, in_degree)
@@ -80,10 +83,13 @@ def aggregate_into(out, h, src_idx, dst_idx, edge_weight=None, in_degree=None):
 # graph (examples/graphed_step.py), where a node costs the GPU 15-20 us whatever it does.
 
 def sage_finish_z(z, h, deg, num_dst, din):
-    """z[:, :din] = h[:num_dst]; inv = 1 / max(deg, 1); z[:, din:] *= inv.  Returns inv (fp32 [num_dst])."""
+    """z[:, :din] = h[:num_dst] (h fp32, or fp16 and upcast); inv = 1 / max(deg, 1); z[:, din:] *= inv.  Returns inv
+    (fp32 [num_dst])."""
+    assert h.dtype in (torch.float32, torch.float16)
     inv = torch.empty(num_dst, dtype=torch.float32, device=z.device)
-    _lib._check(_lib.load().fgnn_sage_finish_z(_ptr(z), z.stride(0), _ptr(h), h.stride(0), _ptr(deg), _ptr(inv), num_dst,
-                                               din, _st(z)), "fgnn_sage_finish_z")
+    what = "fgnn_sage_finish_z" + ("_f16" if h.dtype == torch.float16 else "")
+    _lib._check(getattr(_lib.load(), what)(_ptr(z), z.stride(0), _ptr(h), h.stride(0), _ptr(deg), _ptr(inv), num_dst, din,
+                                           _st(z)), what)
     return inv
 
 
@@ -151,8 +157,9 @@ def aggregate_scaled_into(out, h, src_idx, dst_idx, edge_weight=None, src_deg=No
     """out[dst_idx[e]] += f_dst(dst_deg[dst_idx[e]]) * edge_weight[e] * f_src(src_deg[src_idx[e]]) * h[src_idx[e]] into a
     caller-initialised fp32 tensor, no autograd (modes: 0 factor 1, 1 rsqrt(max(d, 1)), 2 1 / max(d, 1)).  `out` AND `h`
     may be column blocks of wider row-major matrices (unit stride inside a row).  The backward pass of a layer is the
-    same call with the index tensors, the degree vectors and the modes swapped."""
-    assert h.dtype == torch.float32 and out.dtype == torch.float32
+    same call with the index tensors, the degree vectors and the modes swapped.  h: fp32, or fp16 rows that are upcast
+    on load."""
+    assert h.dtype in (torch.float32, torch.float16) and out.dtype == torch.float32
     assert h.dim() == 2 and h.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
     assert src_idx.dtype == torch.int32 and dst_idx.dtype == torch.int32
     assert src_idx.is_contiguous() and dst_idx.is_contiguous() and src_idx.numel() == dst_idx.numel()

@@ -130,9 +130,11 @@ def learnable_labels(indptr, indices, feat, num_class, seed=5):
 
 
 def write_dataset(root, name, num_node, num_edge, feat_dim, num_class, num_train, num_valid=0, num_test=0,
-                  seed=42, with_prefix=False, with_alias=False, learnable=False):
+                  seed=42, with_prefix=False, with_alias=False, learnable=False, feat_f16=False):
     """Writes <root>/<name>/{meta.txt,indptr.bin,indices.bin,feat.bin,label.bin,*_set.bin}.  learnable: labels that
-    follow from the features and the graph (learnable_labels) instead of uniform random ones."""
+    follow from the features and the graph (learnable_labels) instead of uniform random ones.  feat_f16: also
+    feat_f16.bin, the table of the engine's `feat_store_dtype = f16` (feat.bin rounded to IEEE binary16 -- what
+    `fgnn_dataset feat-f16` writes)."""
     d = os.path.join(root, name)
     os.makedirs(d, exist_ok=True)
     indptr, indices = powerlaw_csr(num_node, num_edge, seed)
@@ -144,6 +146,8 @@ def write_dataset(root, name, num_node, num_edge, feat_dim, num_class, num_train
     indices.tofile(os.path.join(d, "indices.bin"))
     feat = node_features(num_node, feat_dim, seed + 2)
     feat.tofile(os.path.join(d, "feat.bin"))
+    if feat_f16:
+        feat.astype(np.float16).tofile(os.path.join(d, "feat_f16.bin"))
     random_labels = rng.integers(0, num_class, size=num_node, dtype=np.uint64)  # (drawn either way: same sets below)
     (learnable_labels(indptr, indices, feat, num_class) if learnable else random_labels).tofile(
         os.path.join(d, "label.bin"))

@@ -69,6 +69,12 @@ int fgnn_host_queue_flip_word(const char *shm_name, size_t key, size_t word);
  * out[0] = #layers, out[1] = fanout[0], out[2] = run_arch, out[3] = UseGPUCache. */
 int fgnn_host_config_probe(const char **keys, const char **vals, size_t n, size_t out[4]);
 
+/* Parses a config and loads its dataset through the same code as samgraph_config + samgraph_init (host side only), for
+ * the optional key feat_store_dtype: out[0] = the feature table's dtype code (fgnn_hip.h: FGNN_F32 0, FGNN_F16 2),
+ * out[1] = its element size, out[2] = the bytes of the host table, out[3] = 1 if it was read from a file.  An unknown
+ * value, or f16 without feat_f16.bin, aborts like every config error. */
+int fgnn_host_feat_store_probe(const char **keys, const char **vals, size_t n, size_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

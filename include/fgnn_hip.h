@@ -402,6 +402,19 @@ int fgnn_block_degrees(const uint32_t *src_index, const uint32_t *dst_index, con
 int fgnn_block_aggregate_scaled(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
                                 size_t num_edge, const float *h, size_t h_ld, size_t dim, float *out, size_t out_ld,
                                 const float *src_deg, int src_mode, const float *dst_deg, int dst_mode, void *stream);
+/* fgnn_block_aggregate_ex and fgnn_block_aggregate_scaled over half-precision rows: h holds IEEE binary16 values (the
+ * input features of a `feat_store_dtype = f16` store), h_ld counts elements, everything else -- weights, degree
+ * vectors, sums, out -- stays fp32.  The upcast is exact and every output element's additions are those of the fp32
+ * entry point on the upcast rows, in the same order.  Checks as above, except that h need only be 2-byte aligned;
+ * rows whose base or stride is not 4-byte aligned (an odd address / 2, h_ld or dim) are read one column per lane
+ * instead of two. */
+int fgnn_block_aggregate_ex_f16(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
+                                size_t num_edge, const void *h, size_t dim, float *out, size_t out_ld, float *in_degree,
+                                void *stream);
+int fgnn_block_aggregate_scaled_f16(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
+                                    size_t num_edge, const void *h, size_t h_ld, size_t dim, float *out, size_t out_ld,
+                                    const float *src_deg, int src_mode, const float *dst_deg, int dst_mode,
+                                    void *stream);
 /* out = relu(x) / ||relu(x)||_2 row by row (a row without a positive entry stays zero); inv_norm[rows] receives
  * 1 / norm (1 for zero rows) for the backward pass.  out must not alias x. */
 int fgnn_relu_l2norm(const float *x, size_t x_ld, float *out, size_t out_ld, float *inv_norm, size_t rows, size_t dim,
@@ -456,6 +469,9 @@ int fgnn_gat_backward(const uint32_t *src_index, const uint32_t *dst_index, size
  * aligned rows. */
 int fgnn_sage_finish_z(float *z, size_t ld, const float *h, size_t h_ld, const float *deg, float *inv, size_t num_dst,
                        size_t din, void *stream);
+/* the same with binary16 rows in h (h_ld in elements, % 4 == 0; h 8-byte aligned): z[i, :din] = (float)h[i, :din] */
+int fgnn_sage_finish_z_f16(float *z, size_t ld, const void *h, size_t h_ld, const float *deg, float *inv, size_t num_dst,
+                           size_t din, void *stream);
 /* its backward half: gh[i, :] = gz[i, :din] for i < num_dst, 0 for num_dst <= i < num_src (the self path; the neighbour
  * path is then ADDED by fgnn_block_aggregate with row / col swapped); gagg[i, :] = gz[i, din:] * inv[i]. */
 int fgnn_sage_grad_prep(const float *gz, size_t gz_ld, const float *inv, float *gh, float *gagg, size_t num_dst,

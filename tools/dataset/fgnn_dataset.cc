@@ -10,6 +10,10 @@
 //   fgnn_dataset prob-prefix-table <dir> [policy]        -> prob_prefix_table.bin (f32[E], per-row inclusive sums)
 //   fgnn_dataset alias-table       <dir> [policy]        -> prob_table.bin (f32[E]) + alias_table.bin (u32[E], node ids)
 //   fgnn_dataset coo-to-dataset    <dir> <coo.bin>       -> indptr.bin, indices.bin, {train,valid,test}_set.bin
+//   fgnn_dataset feat-f16          <dir> [--allow-inf]   -> feat_f16.bin (IEEE binary16 [N x D] from feat.bin, round to
+//                                                           nearest even; the table of `feat_store_dtype = f16`).  Prints
+//                                                           how many finite values became infinite; fails if any did,
+//                                                           unless --allow-inf
 //   fgnn_dataset check             <dir>                 -> validates meta.txt against the CSR files
 //
 // What each file must contain follows the reference's generators (utility/data-process/toolkit/cache/
@@ -422,11 +426,75 @@ int Check(const Dataset &d) {
   return 0;
 }
 
+// IEEE binary32 -> binary16 bits: round to nearest even, subnormals kept, overflow to infinity, NaN stays NaN (sign and
+// the top payload bits kept, a payload that would vanish becomes 1) -- what numpy's astype(float16) produces
+uint16_t HalfBits(uint32_t f) {
+  const uint16_t sign = (uint16_t)((f >> 16) & 0x8000u);
+  const uint32_t abs = f & 0x7fffffffu;
+  if (abs > 0x7f800000u) {
+    const uint16_t r = (uint16_t)(0x7c00u + ((abs & 0x7fffffu) >> 13));
+    return sign | (r == 0x7c00u ? 0x7c01u : r);
+  }
+  if (abs >= 0x477ff000u) return sign | 0x7c00u;  // 65520 = the tie between 65504 and 2^16, and everything above
+  const uint32_t e = abs >> 23;
+  uint32_t r, rem, half;
+  if (e < 113) {  // below 2^-14: a multiple of 2^-24
+    const uint32_t shift = 126 - e;
+    if (shift > 24) return sign;  // below 2^-25: zero
+    const uint32_t mant = (abs & 0x7fffffu) | 0x800000u;
+    r = mant >> shift, rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  } else {
+    r = ((e - 112) << 10) | ((abs & 0x7fffffu) >> 13), rem = abs & 0x1fffu, half = 0x1000u;
+  }
+  if (rem > half || (rem == half && (r & 1u))) ++r;  // a carry out of the mantissa lands in the exponent
+  return sign | (uint16_t)r;
+}
+
+// feat.bin (f32 [N x D]) -> feat_f16.bin, a bounded slice at a time (the table may be larger than memory)
+int FeatF16(std::string dir, bool allow_inf) {
+  if (dir.empty() || dir.back() != '/') dir += '/';
+  const auto meta = ReadMeta(dir);
+  const size_t count = meta.at("NUM_NODE") * meta.at("FEAT_DIM");
+  std::ifstream in(dir + "feat.bin", std::ios::binary | std::ios::ate);
+  if (!in) Die("cannot open " + dir + "feat.bin");
+  if ((size_t)in.tellg() != count * 4) Die(dir + "feat.bin: expected " + std::to_string(count * 4) + " bytes, found " + std::to_string((size_t)in.tellg()));
+  in.seekg(0);
+  const std::string path = dir + "feat_f16.bin";
+  std::ofstream out(path, std::ios::binary | std::ios::trunc);
+  if (!out) Die("cannot write " + path);
+  constexpr size_t kSlice = (size_t)1 << 22;  // 16 MB in, 8 MB out
+  std::vector<uint32_t> src(std::min(count, kSlice));
+  std::vector<uint16_t> dst(src.size());
+  size_t became_inf = 0;
+  for (size_t base = 0; base < count; base += kSlice) {
+    const size_t n = std::min(kSlice, count - base);
+    in.read(reinterpret_cast<char *>(src.data()), (std::streamsize)(n * 4));
+    if (!in) Die("short read from " + dir + "feat.bin");
+#pragma omp parallel for reduction(+ : became_inf)
+    for (size_t i = 0; i < n; ++i) {
+      dst[i] = HalfBits(src[i]);
+      became_inf += (dst[i] & 0x7fffu) == 0x7c00u && (src[i] & 0x7fffffffu) < 0x7f800000u;
+    }
+    out.write(reinterpret_cast<const char *>(dst.data()), (std::streamsize)(n * 2));
+  }
+  out.close();
+  if (!out) Die("cannot write " + path);
+  printf("wrote %s (%zu bytes)\n", path.c_str(), count * 2);
+  printf("finite values that became infinite: %zu\n", became_inf);
+  if (became_inf && !allow_inf) {
+    remove(path.c_str());
+    Die(std::to_string(became_inf) + " finite values exceed the binary16 range (>= 65520 in magnitude); " + path +
+        " removed -- rescale the features, or pass --allow-inf to keep the infinities");
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
-  if (argc < 3) Die("usage: fgnn_dataset <cache-by-degree|cache-by-random|cache-by-heuristic|cache-by-degree-hop|cache-by-fake-optimal|32to64|prob-prefix-table|alias-table|coo-to-dataset|check> <dir> [arg]");
+  if (argc < 3) Die("usage: fgnn_dataset <cache-by-degree|cache-by-random|cache-by-heuristic|cache-by-degree-hop|cache-by-fake-optimal|32to64|prob-prefix-table|alias-table|coo-to-dataset|feat-f16|check> <dir> [arg]");
   const std::string cmd = argv[1];
+  if (cmd == "feat-f16") return FeatF16(argv[2], argc > 3 && std::string(argv[3]) == "--allow-inf");
   if (cmd == "coo-to-dataset") {
     if (argc < 4) Die("coo-to-dataset needs <dir> <coo.bin>");
     return CooToDataset(argv[2], argv[3]);

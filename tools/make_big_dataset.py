@@ -2,8 +2,10 @@
 """Writes a papers100M-/products-shaped synthetic dataset in the engine's on-disk layout WITHOUT feat.bin (run the
 engine with SAMGRAPH_EMPTY_FEAT=k, like the reference's papers100M_empty): the CSR comes from bench.py's GPU generator,
 so a 1.6 G-edge graph is written in seconds.
-usage: make_big_dataset.py <dir> [papers100M|products|twitter|uk-2006-05] [--prefix]   (--prefix: also
-prob_prefix_table.bin for the weighted_khop_prefix sampler)"""
+usage: make_big_dataset.py <dir> [papers100M|products|twitter|uk-2006-05] [--prefix] [--feat-f16]   (--prefix: also
+prob_prefix_table.bin for the weighted_khop_prefix sampler; --feat-f16: also feat_f16.bin, standard-normal features
+as IEEE binary16 for runs with `feat_store_dtype = f16` and real rows -- half the 57 GB an fp32 table of the papers100M
+shape would take)"""
 import os
 import sys
 
@@ -42,6 +44,13 @@ if "--prefix" in sys.argv:
         for a in range(0, ne, chunk):
             f.write(pre[a:a + chunk].cpu().numpy().tobytes())
     del pre
+if "--feat-f16" in sys.argv:
+    rows = max(1, (1 << 26) // w["feat_dim"])  # 256 MB of fp32 at a time
+    with open(os.path.join(out, "feat_f16.bin"), "wb") as f:
+        for a in range(0, w["num_node"], rows):
+            n = min(rows, w["num_node"] - a)
+            x = torch.randn((n, w["feat_dim"]), generator=g, device=dev, dtype=torch.float32)
+            f.write(x.cpu().numpy().astype(np.float16).tobytes())
 with open(os.path.join(out, "meta.txt"), "w") as f:
     f.write(f"NUM_NODE {w['num_node']}\nNUM_EDGE {ne}\nFEAT_DIM {w['feat_dim']}\nNUM_CLASS {w['num_class']}\n"
             f"NUM_TRAIN_SET {n_tr}\nNUM_VALID_SET 1000\nNUM_TEST_SET 1000\n")

@@ -27,6 +27,10 @@ ap.add_argument("--workload", default=None, help="gcn / pinsage: bench.py worklo
 ap.add_argument("--kernel-lib", default=None, metavar="PATH",
                 help="another build of libfgnn_hip.so to bind (lib.use_library), e.g. an earlier commit's: the C ABI is "
                      "the yardstick, so one Python tree times either build")
+ap.add_argument("--feat-store", default="f32", choices=["f32", "f16"],
+                help="f16: A/B of the fused model fed fp32 input features against the same model fed the same features "
+                     "as fp16 rows (interleaved alternations in one process, median and spread of --ab), for the "
+                     "layer-0 aggregation alone and for the whole step; graphsage takes the papers100M-shaped batch")
 args = ap.parse_args()
 if args.fused is not None:
     os.environ["SAGE_FUSED"] = str(args.fused)
@@ -136,6 +140,76 @@ class Block:
         return self.ndst
 
 
+def feat_store_main():
+    """--feat-store f16: one fused model, one batch; variant f32 reads x, variant f16 reads x.half() (no upcast pass:
+    the first layer's kernels convert on load).  Timed with events around --ab-steps calls, --ab interleaved
+    alternations; reports median and spread per variant and the bytes of input rows the aggregation reads."""
+    import statistics
+    from fgnn_hip.nn import Adam, aggregate_into, aggregate_scaled_into, block_degrees, softmax_xent
+    dev = "cuda:0"
+    torch.cuda.set_device(0)
+    workload = args.workload or {"graphsage": "papers100M", "gcn": "twitter", "pinsage": "uk-2006-05",
+                                 "gat": "products"}[args.model]
+    blocks, w = real_batch_blocks(workload, dev)
+    b0 = blocks[0]
+    print("%s batch of %s: %s" % (args.model, workload, ", ".join(
+        "%d src -> %d dst, %d edges" % (b.nsrc, b.ndst, b.row.numel()) for b in blocks)))
+    g = torch.Generator(device=dev).manual_seed(0)
+    x16 = torch.randn(b0.nsrc, w["feat_dim"], device=dev, generator=g).half()
+    xs = {"f32": x16.float(), "f16": x16}
+    y = torch.randint(0, w["num_class"], (blocks[-1].ndst,), device=dev, generator=g)
+    torch.manual_seed(0)
+    model = MODELS[args.model](w["feat_dim"], 256, w["num_class"], len(blocks), 0.5, fused=True).to(dev)
+    opt = Adam(model.parameters(), lr=0.003)
+    model.dropout_step = opt.step_count
+    out0 = torch.zeros((b0.ndst, w["feat_dim"]), device=dev)
+    sdeg, ddeg = block_degrees(b0.row, b0.col, b0.nsrc, b0.ndst)
+
+    def step(x):
+        out = model(blocks, x)
+        loss, grad = softmax_xent(out, y)
+        opt.zero_grad()
+        out.backward(grad)
+        opt.step()
+
+    def aggregate(x):
+        if args.model == "gcn":
+            aggregate_scaled_into(out0, x, b0.row, b0.col, None, sdeg, 1, ddeg, 1)
+        else:
+            aggregate_into(out0, x, b0.row, b0.col)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def run(fn, x, n):
+        e0.record()
+        for _ in range(n):
+            fn(x)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+    touched = int(torch.unique(b0.row).numel())
+    for what, fn in (("layer-0 aggregation", aggregate), ("whole step", step)):
+        for k in xs:
+            run(fn, xs[k], 10)
+        ms = {k: [] for k in xs}
+        for _ in range(args.ab):
+            for k in xs:
+                ms[k].append(run(fn, xs[k], args.ab_steps))
+        for k, v in ms.items():
+            print("%s, %s rows: median %.4f ms, min %.4f, max %.4f, spread %.4f  (%s)"
+                  % (what, k, statistics.median(v), min(v), max(v), max(v) - min(v), " ".join("%.4f" % t for t in v)))
+        gain = statistics.median(ms["f32"]) - statistics.median(ms["f16"])
+        spread = max(max(v) - min(v) for v in ms.values())
+        print("%s: f32 median - f16 median = %.4f ms, larger spread %.4f ms: f16 %s" % (
+            what, gain, spread, "FASTER" if gain > spread else "NOT FASTER beyond the spread"))
+    print("input rows read per aggregation: %d edges x %d B (f32) / %d B (f16) = %.1f / %.1f MB; distinct source rows "
+          "%d = %.1f / %.1f MB" % (b0.row.numel(), 4 * w["feat_dim"], 2 * w["feat_dim"],
+                                   b0.row.numel() * 4e-6 * w["feat_dim"], b0.row.numel() * 2e-6 * w["feat_dim"], touched,
+                                   touched * 4e-6 * w["feat_dim"], touched * 2e-6 * w["feat_dim"]))
+
+
+if args.feat_store == "f16":
+    feat_store_main()
+    sys.exit(0)
 if args.model != "graphsage":
     ab_main()
     sys.exit(0)
