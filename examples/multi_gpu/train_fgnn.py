@@ -32,7 +32,8 @@ from models import MODELS  # noqa: E402
 
 
 # run-config entries that belong to the script, not to sam.config()
-SCRIPT_KEYS = ("sample_workers", "train_workers", "model", "no_train", "report_acc", "op_by_op", "async_train")
+SCRIPT_KEYS = ("sample_workers", "train_workers", "model", "no_train", "report_acc", "op_by_op", "async_train",
+               "exact_eval")
 
 
 def build_parser():
@@ -43,6 +44,9 @@ def build_parser():
     ap.add_argument("--report-acc", type=int, default=0,
                     help="trainer 0: validation accuracy every N of its steps and test accuracy at the end (the "
                          "reference's --report-acc, multi_gpu/train_graphsage.py:65,214-220,344-347,395-397); 0: off")
+    ap.add_argument("--exact-eval", action="store_true",
+                    help="--report-acc by exact layer-wise inference over the full graph (examples/inference.py; graphsage "
+                         "and gcn) instead of sampled evaluation batches")
     ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
     ap.add_argument("--sample-type", default=None)
     ap.add_argument("--fanout", nargs="+", type=int, default=None)
@@ -108,7 +112,7 @@ def get_run_config(args):
         rc["train_workers"] = ["cuda:%d" % (ns + i) for i in range(nt)]
     rc.update(model=args.model, num_hidden=args.num_hidden, lr=args.lr, dropout=args.dropout,
               pipeline=not args.no_pipeline, no_train=args.no_train, report_acc=args.report_acc, op_by_op=args.op_by_op,
-              async_train=args.async_train)
+              async_train=args.async_train, exact_eval=args.exact_eval)
     return rc
 
 
@@ -157,7 +161,8 @@ def run_train(worker_id, rc):
     if rc["report_acc"] and worker_id == 0 and rc["model"] != "pinsage":
         import train_accuracy
         graph, valid_set, test_set, feat, label = train_accuracy.load_accuracy_data(rc["dataset_path"])
-        accuracy = train_accuracy.Accuracy(graph, valid_set, test_set, feat, label, rc["fanout"], rc["batch_size"], dev)
+        accuracy = train_accuracy.Accuracy(graph, valid_set, test_set, feat, label, rc["fanout"], rc["batch_size"], dev,
+                                           exact=rc["exact_eval"])
     ddp = nt > 1 and shared is None
     if ddp:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[dev], output_device=dev)

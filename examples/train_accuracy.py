@@ -8,7 +8,12 @@ training pipeline's queue.  Same structure here, without DGL: the evaluation bat
 kernel-level sampler (fgnn_hip.lib.Sampler, khop0 -- uniform without replacement, the CSR copy stays untouched)
 on the evaluation device, features and labels are gathered by the same kernels, and the model sees the same block
 objects as in training (samgraph.torch.adapter.CooBlock; DGLBlocks when DGL is installed).
+
+Accuracy(..., exact=True) evaluates without a sampler instead: one exact layer-wise inference pass over the full graph
+per call (examples/inference.py), the predictions of the set's nodes read from its result -- an accuracy that does not
+depend on a seed.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -48,9 +53,11 @@ class Accuracy:
     constructor.  Graph, features and labels are uploaded to `sample_device` once (evaluation datasets of the sizes
     the examples train on fit; for larger ones pass feat / label slices that cover the evaluation sets' neighbourhoods)."""
 
-    def __init__(self, graph, valid_set, test_set, feat, label, fanout, batch_size, sample_device, seed=0xACC):
+    def __init__(self, graph, valid_set, test_set, feat, label, fanout, batch_size, sample_device, seed=0xACC,
+                 exact=False):
         self.dev = torch.device(sample_device)
         self.fanout, self.batch_size = list(fanout), int(batch_size)
+        self.exact = bool(exact)
 
         def up(a):
             a = np.ascontiguousarray(a)
@@ -59,18 +66,31 @@ class Accuracy:
             if a.dtype == np.uint64:
                 a = a.view(np.int64)
             return torch.from_numpy(a).to(self.dev)
-        with torch.cuda.device(self.dev):
+        # (exact evaluation also runs on CPU tensors: op by op, examples/inference.py)
+        with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
             self.indptr, self.indices = up(graph[0]), up(graph[1])
             self.feat, self.label = up(feat), up(label)
             self.valid_set, self.test_set = up(valid_set), up(test_set)
-            # its own sampler, own CSR copy, own RNG stream: nothing of the training engine's state is touched
-            self.sampler = lib.Sampler(self.indptr, self.indices, self.fanout, self.batch_size, sample_type=lib.KHOP0,
-                                       seed=seed)
-            self.batch = self.sampler.new_batch(self.feat.shape[1], lib.F32, lib.I64)
+            if not self.exact:  # (exact: full-neighbourhood inference -- no sampler, `seed` plays no part)
+                # its own sampler, own CSR copy, own RNG stream: nothing of the training engine's state is touched
+                self.sampler = lib.Sampler(self.indptr, self.indices, self.fanout, self.batch_size,
+                                           sample_type=lib.KHOP0, seed=seed)
+                self.batch = self.sampler.new_batch(self.feat.shape[1], lib.F32, lib.I64)
         self.seq = 0
         self.calls = 0
 
+    def _evaluate_exact(self, model, ids, train_device):
+        from inference import layerwise_inference
+        if ids.numel() == 0:
+            return 0.0
+        logits = layerwise_inference(model, self.indptr, self.indices, self.feat, device=train_device)
+        ids = (ids.long() & 0xFFFFFFFF).to(train_device)
+        pred = logits[ids].argmax(1)
+        return int((pred == self.label.to(train_device)[ids]).sum()) / ids.numel()
+
     def _evaluate(self, model, ids, train_device):
+        if self.exact:
+            return self._evaluate_exact(model, ids, train_device)
         total = correct = 0
         was_training = model.training
         model.eval()

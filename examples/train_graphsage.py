@@ -61,6 +61,13 @@ def main():
     ap.add_argument("--report-acc", type=int, default=0,
                     help="validation accuracy every N steps and test accuracy at the end (the reference's --report-acc, "
                          "multi_gpu/train_graphsage.py:65,344-347,395-397); 0: off")
+    ap.add_argument("--exact-eval", action="store_true",
+                    help="--report-acc by exact layer-wise inference over the full graph (examples/inference.py; graphsage "
+                         "and gcn) instead of sampled evaluation batches: no sampler, no dependence on --eval-seed")
+    ap.add_argument("--eval-seed", type=lambda v: int(v, 0), default=0xACC, help="seed of the sampled evaluation")
+    ap.add_argument("--save-predictions", default=None, metavar="FILE.npy",
+                    help="after the last epoch, write the [N, n_classes] logits of every node (exact layer-wise "
+                         "inference over the full graph) to FILE.npy")
     ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
     # GAT (example/samgraph/train_gat.py: 8 heads x 32 hidden, attention dropout = feature dropout)
     ap.add_argument("--num-heads", type=int, default=8, help="gat: attention heads of the inner layers")
@@ -122,7 +129,7 @@ def main():
         import train_accuracy
         graph, valid_set, test_set, feat, label = train_accuracy.load_accuracy_data(args.dataset_path)
         accuracy = train_accuracy.Accuracy(graph, valid_set, test_set, feat, label, args.fanout, args.batch_size,
-                                           th.device(sampler_ctx))
+                                           th.device(sampler_ctx), seed=args.eval_seed, exact=args.exact_eval)
     loss_fcn = nn.CrossEntropyLoss()
     opt = th.optim.Adam(model.parameters(), lr=args.lr, fused=True)  # one kernel per step instead of one per tensor and op
     num_epoch, num_step = sam.num_epoch(), sam.steps_per_epoch()
@@ -163,6 +170,13 @@ def main():
         acc = accuracy.test_acc(model, dev)
         print("Test Acc: {:.2f}% | Acc Time: {:.4f}".format(acc * 100.0, time.time() - tt))
         print("test_result:test_acc={:.4f}".format(acc))
+    if args.save_predictions:
+        import train_accuracy
+        from inference import layerwise_inference
+        graph, _, _, feat, _ = train_accuracy.load_accuracy_data(args.dataset_path)
+        logits = layerwise_inference(model, np.asarray(graph[0]), np.asarray(graph[1]), np.asarray(feat), device=dev)
+        np.save(args.save_predictions, logits.cpu().numpy())
+        print("predictions of {:d} nodes written to {:}".format(logits.shape[0], args.save_predictions))
     sam.report_step_average(num_epoch - 1, num_step - 1)
     # test_result lines in the reference's format (multi_gpu/train_graphsage.py:198-199)
     for k, v in (("epoch_time:total", np.mean(epoch_total[1:])), ("epoch_time:sample_time", np.mean(epoch_sample[1:])),

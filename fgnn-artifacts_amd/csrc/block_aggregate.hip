@@ -17,23 +17,10 @@
 // fgnn_block_aggregate_ex_f16 / _scaled_f16 (the first layer over a half-precision feature store): the rows of h are
 // IEEE binary16, converted on load (exact); weights, sums and out stay fp32, so an output element sees the very
 // additions, in the very order, that the fp32 entry points make on the upcast rows.
-#include <hip/hip_fp16.h>
-
-#include "fgnn_device.h"
+#include "aggregate_rows.h"
 
 namespace fgnn {
 namespace {
-
-// What a lane loads of a row per slot -- the kernel's Row parameter: float (fp32 rows), __half2 (fp16 rows whose base
-// and stride are 4-byte aligned: two columns per lane, so that a wave's load still covers 256 contiguous bytes) or
-// __half (fp16 rows with an odd base, stride or dim: one column per lane, correct at half the width).
-template <typename Row> constexpr int kRowCols = 1;
-template <> constexpr int kRowCols<__half2> = 2;
-template <typename Row> __device__ __forceinline__ Row row_zero() { return Row(0.0f); }
-template <> __device__ __forceinline__ __half2 row_zero<__half2>() { return __half2(__half(0.0f), __half(0.0f)); }
-__device__ __forceinline__ float row_col(float r, int) { return r; }
-__device__ __forceinline__ float row_col(__half r, int) { return __half2float(r); }
-__device__ __forceinline__ float row_col(__half2 r, int j) { return j ? __high2float(r) : __low2float(r); }
 
 // Lane l owns slots l, l + 64, ... (P of them per pass over the edges), a slot being kRowCols<Row> adjacent columns:
 // every load of a wave instruction covers 64 consecutive slots (256 bytes of a row for float and __half2), every float
@@ -175,15 +162,8 @@ int launch_block_aggregate(const char *what, bool scaled, bool h_f16, const uint
                            size_t h_ld, size_t dim, float *out, size_t out_ld, float *in_degree, const float *src_deg,
                            int src_mode, const float *dst_deg, int dst_mode, void *stream) {
   if (num_edge == 0) return FGNN_OK;
-  if (!src_index || !dst_index || !h || !out || dim == 0 || !fits_u32(dim) || h_ld < dim || !fits_u32(h_ld) ||
-      out_ld < dim || !fits_u32(out_ld))
-    return FGNN_EINVAL;
-  if (src_mode < 0 || src_mode > 2 || dst_mode < 0 || dst_mode > 2 || (src_mode && !src_deg) || (dst_mode && !dst_deg))
-    return FGNN_EINVAL;
-  const uintptr_t h_addr = reinterpret_cast<uintptr_t>(h);
-  if (!float_aligned(src_index) || !float_aligned(dst_index) || !float_aligned(edge_weight) ||
-      (h_f16 ? (h_addr & 1u) != 0 : !float_aligned(h)) || !float_aligned(out) || !float_aligned(in_degree) ||
-      !float_aligned(src_deg) || !float_aligned(dst_deg))
+  if (!src_index || !dst_index || !float_aligned(src_index) || !float_aligned(dst_index) || !float_aligned(in_degree) ||
+      !aggregate_args_ok(h_f16, h, h_ld, dim, out, out_ld, edge_weight, src_deg, src_mode, dst_deg, dst_mode))
     return FGNN_EINVAL;
   const size_t waves = div_up(num_edge, (size_t)kEdgesPerWave);
   const size_t blocks = div_up(waves, (size_t)kWavesPerBlock);
@@ -194,7 +174,7 @@ int launch_block_aggregate(const char *what, bool scaled, bool h_f16, const uint
                                src_deg, src_mode, dst_deg, dst_mode);
   };
   if (!h_f16) launch(float());
-  else if (((h_addr & 3u) | (h_ld & 1u) | (dim & 1u)) == 0) launch(__half2());
+  else if (half_rows_paired(h, h_ld, dim)) launch(__half2());
   else launch(__half());
   return launch_status(what);
 }

@@ -106,6 +106,10 @@ SIGNATURES = {
     "fgnn_block_aggregate_scaled": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P)),
     "fgnn_block_aggregate_ex_f16": (_I, (_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, _P)),
     "fgnn_block_aggregate_scaled_f16": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P)),
+    "fgnn_csr_split_length": (_Z, ()),
+    "fgnn_csr_aggregate_workspace_bytes": (_Z, (_Z, _Z, _Z)),
+    "fgnn_csr_aggregate": (_I, (_P, _P, _P, _P, _Z, _Z, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P, _Z, _P)),
+    "fgnn_csr_aggregate_f16": (_I, (_P, _P, _P, _P, _Z, _Z, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P, _Z, _P)),
     "fgnn_relu_l2norm": (_I, (_P, _Z, _P, _Z, _P, _Z, _Z, _P)),
     "fgnn_relu_l2norm_backward": (_I, (_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P)),
     "fgnn_gat_workspace_bytes": (_Z, (_Z, _Z, _Z)),

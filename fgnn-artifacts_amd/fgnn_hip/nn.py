@@ -168,6 +168,64 @@ def aggregate_scaled_into(out, h, src_idx, dst_idx, edge_weight=None, src_deg=No
     return _aggregate(out, h, src_idx, dst_idx, edge_weight, scaling=(src_deg, src_mode, dst_deg, dst_mode))
 
 
+# ---- aggregation over whole CSR rows: exact layer-wise inference (csrc/csr_aggregate.hip; examples/inference.py) ---------
+
+_CSR_WS = {}
+
+
+def csr_split_length():
+    """edges of a piece: CSR rows longer than this are cut up and summed by several waves (fgnn_csr_split_length)"""
+    return int(_lib.load().fgnn_csr_split_length())
+
+
+def csr_workspace(device, num_rows, max_edges, dim):
+    """the scratch of fgnn_csr_aggregate for these sizes on `device` (hub queue, piece descriptors, partial rows), cached
+    per (device, bytes) like gat_workspace; the call expects nothing of its contents.  Calls that run concurrently on
+    different streams need workspaces of their own."""
+    nbytes = _lib.load().fgnn_csr_aggregate_workspace_bytes(num_rows, max_edges, dim)
+    key = (torch.device(device), nbytes)
+    ws = _CSR_WS.get(key)
+    if ws is None:
+        ws = _CSR_WS[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    return ws, nbytes
+
+
+def csr_aggregate_into(out, h, indptr, indices, nodes=None, first=0, count=None, edge_weight=None, src_deg=None,
+                       src_mode=0, dst_deg=None, dst_mode=0, max_edges=None):
+    """out[i] = f_dst(v) * sum over v's CSR row of edge_weight[p] * f_src(indices[p]) * h[indices[p]] for v = nodes[i], or
+    v = first + i for i < count (default: out's rows): fgnn_csr_aggregate, no autograd.  out (fp32) is OVERWRITTEN --
+    no zero fill, rows without a neighbour become zeros --, h is fp32 or fp16 (upcast on load); both may be column blocks
+    of wider row-major matrices.  indptr / indices: the int32-viewed u32 CSR tensors the engine uses; edge_weight fp32
+    per CSR entry; src_deg / dst_deg fp32 per NODE with the modes of aggregate_scaled_into, dst_deg=None with a
+    dst_mode taking the row's own length.  No float atomics: a row's bits depend on the row alone, whatever else the
+    call computes.  max_edges: upper bound of the summed lengths of the call's rows (default: the graph's edge count,
+    which holds unless `nodes` repeats ids; rows beyond the bound are still right, only summed by one wave each)."""
+    assert h.dtype in (torch.float32, torch.float16) and out.dtype == torch.float32
+    assert h.dim() == 2 and h.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    for t in (edge_weight, src_deg, dst_deg):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert edge_weight is None or edge_weight.numel() == indices.numel()
+    if nodes is not None:
+        assert nodes.dtype == torch.int32 and nodes.is_contiguous() and count is None
+        count = nodes.numel()
+    elif count is None:
+        count = out.shape[0]
+    assert out.shape[0] >= count and (nodes is not None or first + count <= indptr.numel() - 1)
+    _lib._need_gpu(out, h, indptr, indices, nodes, edge_weight, src_deg, dst_deg)
+    dim = h.shape[1]
+    if max_edges is None:
+        max_edges = indices.numel()
+    ws, nbytes = csr_workspace(h.device, count, max_edges, dim)
+    what = "fgnn_csr_aggregate" + ("_f16" if h.dtype == torch.float16 else "")
+    code = getattr(_lib.load(), what)(_ptr(indptr), _ptr(indices), _ptr(edge_weight), _ptr(nodes), first, count,
+                                      max_edges, _ptr(h), h.stride(0), dim, _ptr(out), out.stride(0), _ptr(src_deg),
+                                      src_mode, _ptr(dst_deg), dst_mode, _ptr(ws), nbytes, _st(h))
+    _lib._check(code, what)
+    return out
+
+
 class _ReluL2Norm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

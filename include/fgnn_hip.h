@@ -423,6 +423,37 @@ int fgnn_relu_l2norm(const float *x, size_t x_ld, float *out, size_t out_ld, flo
 int fgnn_relu_l2norm_backward(const float *out, size_t out_ld, const float *inv_norm, const float *gout, size_t gout_ld,
                               float *gx, size_t gx_ld, size_t rows, size_t dim, void *stream);
 
+/* ---- aggregation over whole CSR rows (csrc/csr_aggregate.hip; exact layer-wise inference: examples/inference.py) -----
+ * For output row i < num_rows, with v = nodes ? nodes[i] : first + i and the CSR range [indptr[v], indptr[v + 1]):
+ *   out[i * out_ld + c] = f_dst(v) * sum over p of edge_weight[p] * f_src(indices[p]) * h[indices[p] * h_ld + c],  c < dim
+ * (edge_weight NULL = 1, indexed by the position p in indices; f by mode as for fgnn_block_aggregate_scaled, src_deg
+ * and dst_deg indexed by node id; dst_mode != 0 with dst_deg == NULL takes the row's own length as the degree).
+ * out is OVERWRITTEN (no zero fill by the caller), a row without a neighbour writes zeros, columns dim .. out_ld - 1 of
+ * an output row are not touched.  h and out may be column blocks of wider row-major matrices.  No float atomics: one
+ * wave owns an output row.  The order of every output element's additions depends on the row's content and dim only --
+ * not on the grid, on the other rows of the call or on scheduling -- so two calls, and a call over all rows and a call
+ * over a few of them, give bit-identical rows.  Rows of more than fgnn_csr_split_length() edges are cut into pieces of
+ * exactly that many edges, found and queued on the device, summed by different waves into `ws` and combined in piece
+ * order; everything is enqueued on `stream`, without a host synchronisation or a copy to the host.
+ * max_edges: the caller's upper bound of the sum of the lengths of the call's rows (the graph's edge count for distinct
+ * rows); it sizes the workspace, ws_bytes >= fgnn_csr_aggregate_workspace_bytes(num_rows, max_edges, dim), ws 16-byte
+ * aligned (NULL where that size is 0).  Rows beyond a max_edges that did not hold are summed by their owner wave: slower,
+ * the same bits, nothing out of bounds.  num_rows == 0 returns FGNN_OK and touches nothing.  FGNN_EINVAL before any
+ * launch: a null required pointer, a pointer that is not 4-byte aligned (h of the _f16 entry point: 2-byte), dim == 0,
+ * a stride below dim, a mode outside 0 .. 2, src_mode != 0 without src_deg, first + num_rows or max_edges beyond 2^32,
+ * a workspace that is too small.  The _f16 entry point reads IEEE binary16 rows (upcast on load, exact; two columns per
+ * lane unless the base, h_ld or dim is odd); weights, degree vectors, sums and out stay fp32. */
+size_t fgnn_csr_split_length(void);
+size_t fgnn_csr_aggregate_workspace_bytes(size_t num_rows, size_t max_edges, size_t dim);
+int fgnn_csr_aggregate(const uint32_t *indptr, const uint32_t *indices, const float *edge_weight, const uint32_t *nodes,
+                       size_t first, size_t num_rows, size_t max_edges, const float *h, size_t h_ld, size_t dim,
+                       float *out, size_t out_ld, const float *src_deg, int src_mode, const float *dst_deg, int dst_mode,
+                       void *ws, size_t ws_bytes, void *stream);
+int fgnn_csr_aggregate_f16(const uint32_t *indptr, const uint32_t *indices, const float *edge_weight,
+                           const uint32_t *nodes, size_t first, size_t num_rows, size_t max_edges, const void *h,
+                           size_t h_ld, size_t dim, float *out, size_t out_ld, const float *src_deg, int src_mode,
+                           const float *dst_deg, int dst_mode, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- fused GAT layer: edge-softmax attention and its aggregation (csrc/gat_attention.hip; examples/models.py
  * FusedGATConv; reference: dgl.nn.GATConv of example/samgraph/train_gat.py) ------------------------------------------------
  * num_head heads H of num_feat features F each; feat / out / gout / gfeat are [rows, H, F] with a row stride (>= H F
