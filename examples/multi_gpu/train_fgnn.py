@@ -45,8 +45,8 @@ def build_parser():
                     help="trainer 0: validation accuracy every N of its steps and test accuracy at the end (the "
                          "reference's --report-acc, multi_gpu/train_graphsage.py:65,214-220,344-347,395-397); 0: off")
     ap.add_argument("--exact-eval", action="store_true",
-                    help="--report-acc by exact layer-wise inference over the full graph (examples/inference.py; graphsage "
-                         "and gcn) instead of sampled evaluation batches")
+                    help="--report-acc by exact layer-wise inference over the full graph (examples/inference.py; graphsage, "
+                         "gcn and gat) instead of sampled evaluation batches")
     ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
     ap.add_argument("--sample-type", default=None)
     ap.add_argument("--fanout", nargs="+", type=int, default=None)

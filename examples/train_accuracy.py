@@ -80,10 +80,10 @@ class Accuracy:
         self.calls = 0
 
     def _evaluate_exact(self, model, ids, train_device):
-        from inference import layerwise_inference
+        from inference import full_graph_inference
         if ids.numel() == 0:
             return 0.0
-        logits = layerwise_inference(model, self.indptr, self.indices, self.feat, device=train_device)
+        logits = full_graph_inference(model, self.indptr, self.indices, self.feat, device=train_device)
         ids = (ids.long() & 0xFFFFFFFF).to(train_device)
         pred = logits[ids].argmax(1)
         return int((pred == self.label.to(train_device)[ids]).sum()) / ids.numel()

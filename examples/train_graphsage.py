@@ -62,8 +62,8 @@ def main():
                     help="validation accuracy every N steps and test accuracy at the end (the reference's --report-acc, "
                          "multi_gpu/train_graphsage.py:65,344-347,395-397); 0: off")
     ap.add_argument("--exact-eval", action="store_true",
-                    help="--report-acc by exact layer-wise inference over the full graph (examples/inference.py; graphsage "
-                         "and gcn) instead of sampled evaluation batches: no sampler, no dependence on --eval-seed")
+                    help="--report-acc by exact layer-wise inference over the full graph (examples/inference.py; graphsage, "
+                         "gcn and gat) instead of sampled evaluation batches: no sampler, no dependence on --eval-seed")
     ap.add_argument("--eval-seed", type=lambda v: int(v, 0), default=0xACC, help="seed of the sampled evaluation")
     ap.add_argument("--save-predictions", default=None, metavar="FILE.npy",
                     help="after the last epoch, write the [N, n_classes] logits of every node (exact layer-wise "
@@ -172,9 +172,9 @@ def main():
         print("test_result:test_acc={:.4f}".format(acc))
     if args.save_predictions:
         import train_accuracy
-        from inference import layerwise_inference
+        from inference import full_graph_inference
         graph, _, _, feat, _ = train_accuracy.load_accuracy_data(args.dataset_path)
-        logits = layerwise_inference(model, np.asarray(graph[0]), np.asarray(graph[1]), np.asarray(feat), device=dev)
+        logits = full_graph_inference(model, np.asarray(graph[0]), np.asarray(graph[1]), np.asarray(feat), device=dev)
         np.save(args.save_predictions, logits.cpu().numpy())
         print("predictions of {:d} nodes written to {:}".format(logits.shape[0], args.save_predictions))
     sam.report_step_average(num_epoch - 1, num_step - 1)

@@ -10,7 +10,7 @@
 // piece sums in piece order; the destination factor multiplies that once.  Who computes a piece does not enter: rows of
 // at most kCsrSplit edges (one piece) and rows the workspace has no room for are summed by their owner wave, longer
 // rows -- the hubs of a power-law graph, 10^5 .. 10^6 neighbours, tens of milliseconds for one wave -- are appended to a
-// queue in the workspace by the row pass (device-side counters; the queue order varies from run to run), their pieces
+// queue in the workspace by the row pass (csr_queue.h; device-side counters; the queue order varies), their pieces
 // summed into partial rows of the workspace by the waves of a second launch and combined in piece order by a third.
 // So a node's result is bit for bit the same in a call over [0, N) and in a call over 7 nodes, today and tomorrow.
 // Three stream-ordered launches (one where no row of the call can be a hub), one 16-byte memset, no host
@@ -20,38 +20,10 @@
 // Index widths: edge positions are uint32_t (E < 2^32 is the dataset contract); every address into h, out and the
 // partial rows is formed in size_t (111 M rows x 256 columns overflow 32 bits).
 #include "aggregate_rows.h"
+#include "csr_queue.h"
 
 namespace fgnn {
 namespace {
-
-constexpr uint32_t kCsrSplit = 1024;          // edges of a piece
-constexpr uint32_t kNoRow = 0xFFFFFFFFu;      // queue entry / piece descriptor of a hub that found no room
-constexpr size_t kHubGridBlocks = 2048;       // hub passes: at most 8 workgroups per CU, strided over the work
-
-// The workspace of a call: counters (zeroed by the call), the hub queue, one descriptor and one partial row per piece.
-// Capacities are upper bounds from (num_rows, max_edges): a hub has more than kCsrSplit edges, and ceil(L / kCsrSplit)
-// <= L / kCsrSplit + 1 pieces.
-struct CsrWs {
-  uint32_t *counts;   // [4]: hubs queued, pieces handed out, unused
-  uint2 *hubs;        // [hub_cap]   {output row, first piece}
-  uint2 *pieces;      // [piece_cap] {output row, piece of that row}
-  float *partial;     // [piece_cap][dim]
-  uint32_t hub_cap, piece_cap;
-};
-struct CsrWsLayout { size_t hub_cap, piece_cap, hubs_at, pieces_at, partial_at, bytes; };
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-inline CsrWsLayout csr_ws_layout(size_t num_rows, size_t max_edges, size_t dim) {
-  CsrWsLayout l{};
-  const size_t by_edges = max_edges / ((size_t)kCsrSplit + 1);
-  l.hub_cap = num_rows < by_edges ? num_rows : by_edges;
-  if (l.hub_cap == 0) return l;  // no row of the call can be a hub: no workspace
-  l.piece_cap = max_edges / kCsrSplit + l.hub_cap;
-  l.hubs_at = 16;
-  l.pieces_at = l.hubs_at + round16(l.hub_cap * sizeof(uint2));
-  l.partial_at = l.pieces_at + round16(l.piece_cap * sizeof(uint2));
-  l.bytes = l.partial_at + l.piece_cap * dim * sizeof(float);
-  return l;
-}
 
 // The graph, the rows asked for and the scalings: what all three kernels read.
 struct CsrJob {
@@ -65,7 +37,6 @@ __device__ __forceinline__ uint32_t job_node(const CsrJob &j, size_t i) { return
 __device__ __forceinline__ float job_dst_factor(const CsrJob &j, uint32_t v, uint32_t len) {
   return j.dst_mode ? degree_factor(j.dst_deg ? j.dst_deg[v] : (float)len, j.dst_mode) : 1.0f;
 }
-__device__ __forceinline__ uint32_t piece_count(uint32_t len) { return len ? (len - 1) / kCsrSplit + 1 : 1; }
 
 // Lane l owns slots l, l + 64, ... (P per pass over the edges), a slot being kRowCols<Row> adjacent columns, as in
 // block_aggregate_kernel.  acc[q][j] += the products of the cnt (<= kCsrSplit) edges from position p0 on, in CSR order,
@@ -157,23 +128,7 @@ __global__ __launch_bounds__(kBlock) void csr_rows_kernel(CsrJob job, CsrWs ws, 
   const uint32_t v = job_node(job, i);
   const uint32_t beg = job.indptr[v], len = job.indptr[v + 1] - beg;
   const uint32_t np = piece_count(len);
-  if (np > 1 && ws.hub_cap) {  // wave-uniform
-    uint32_t slot = 0, base = 0;
-    if (lane == 0) {
-      slot = atomicAdd(&ws.counts[0], 1u);
-      base = atomicAdd(&ws.counts[1], np);
-    }
-    slot = __shfl(slot, 0, kWave);
-    base = __shfl(base, 0, kWave);
-    const bool fits = slot < ws.hub_cap && base < ws.piece_cap && np <= ws.piece_cap - base;
-    // every queue entry and descriptor below the counters (clamped to the capacities) is written, valid or not
-    if (lane == 0 && slot < ws.hub_cap) ws.hubs[slot] = fits ? make_uint2((uint32_t)i, base) : make_uint2(kNoRow, 0u);
-    if (base < ws.piece_cap) {
-      const uint32_t room = ws.piece_cap - base, wr = np < room ? np : room;
-      for (uint32_t k = lane; k < wr; k += kWave) ws.pieces[base + k] = make_uint2(fits ? (uint32_t)i : kNoRow, k);
-    }
-    if (fits) return;
-  }
+  if (np > 1 && ws.hub_cap && csr_queue_hub(ws, (uint32_t)i, np, lane)) return;  // wave-uniform
   const float fd = job_dst_factor(job, v, len);
   float *op = out + i * out_ld;
   for (uint32_t dbase = 0; dbase < dim; dbase += kWave * P * V) {  // one trip for dim <= 64 P V
@@ -284,22 +239,12 @@ int launch_csr_aggregate(const char *what, bool h_f16, const uint32_t *indptr, c
   if (!indptr || !indices || !float_aligned(indptr) || !float_aligned(indices) || !float_aligned(nodes) ||
       !aggregate_args_ok(h_f16, h, h_ld, dim, out, out_ld, edge_weight, src_deg, src_mode, dst_deg, dst_mode, true))
     return FGNN_EINVAL;
-  // output rows are 32-bit in the queue (kNoRow is no row), node ids are 32-bit, edge positions too
-  if (num_rows >= kNoRow || !fits_u32(max_edges) || (!nodes && (!fits_u32(first) || first + num_rows > 0x100000000ull)) ||
-      div_up(num_rows, (size_t)kWavesPerBlock) > 0x7fffffffull)
-    return FGNN_EINVAL;
+  if (!csr_rows_in_range(nodes != nullptr, first, num_rows, max_edges)) return FGNN_EINVAL;
   const CsrWsLayout l = csr_ws_layout(num_rows, max_edges, dim);
-  if (l.bytes && (!ws || ws_bytes < l.bytes || (reinterpret_cast<uintptr_t>(ws) & 15u) != 0)) return FGNN_EINVAL;
-  if (!fits_u32(l.piece_cap)) return FGNN_EINVAL;
+  if (!csr_ws_ok(l, ws, ws_bytes)) return FGNN_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  CsrWs w{nullptr, nullptr, nullptr, nullptr, 0, 0};
-  if (l.bytes) {
-    char *base = static_cast<char *>(ws);
-    w = CsrWs{reinterpret_cast<uint32_t *>(base), reinterpret_cast<uint2 *>(base + l.hubs_at),
-              reinterpret_cast<uint2 *>(base + l.pieces_at), reinterpret_cast<float *>(base + l.partial_at),
-              (uint32_t)l.hub_cap, (uint32_t)l.piece_cap};
-    FGNN_HIP_CHECK(hipMemsetAsync(w.counts, 0, 16, s));
-  }
+  const CsrWs w = csr_ws_view(l, ws);
+  if (l.bytes) FGNN_HIP_CHECK(hipMemsetAsync(w.counts, 0, 16, s));
   const CsrJob job{indptr, indices, nodes, edge_weight, src_deg, dst_deg, (uint32_t)first, src_mode, dst_mode};
   if (!h_f16) launch_csr<float>(job, w, h, out, num_rows, (uint32_t)dim, (uint32_t)h_ld, (uint32_t)out_ld, s);
   else if (half_rows_paired(h, h_ld, dim))

@@ -110,6 +110,9 @@ SIGNATURES = {
     "fgnn_csr_aggregate_workspace_bytes": (_Z, (_Z, _Z, _Z)),
     "fgnn_csr_aggregate": (_I, (_P, _P, _P, _P, _Z, _Z, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P, _Z, _P)),
     "fgnn_csr_aggregate_f16": (_I, (_P, _P, _P, _P, _Z, _Z, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P, _Z, _P)),
+    "fgnn_csr_gat_max_heads": (_Z, ()),
+    "fgnn_csr_gat_workspace_bytes": (_Z, (_Z, _Z, _Z, _Z)),
+    "fgnn_csr_gat_attention": (_I, (_P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _Z, _Z, _Z, _F, _P, _Z, _P, _Z, _P)),
     "fgnn_relu_l2norm": (_I, (_P, _Z, _P, _Z, _P, _Z, _Z, _P)),
     "fgnn_relu_l2norm_backward": (_I, (_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P)),
     "fgnn_gat_workspace_bytes": (_Z, (_Z, _Z, _Z)),

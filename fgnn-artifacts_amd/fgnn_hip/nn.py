@@ -173,6 +173,15 @@ def aggregate_scaled_into(out, h, src_idx, dst_idx, edge_weight=None, src_deg=No
 _CSR_WS = {}
 
 
+def _csr_ws(device, nbytes):
+    """a workspace of the CSR kernels, cached per (device, bytes)"""
+    key = (torch.device(device), nbytes)
+    ws = _CSR_WS.get(key)
+    if ws is None:
+        ws = _CSR_WS[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+    return ws
+
+
 def csr_split_length():
     """edges of a piece: CSR rows longer than this are cut up and summed by several waves (fgnn_csr_split_length)"""
     return int(_lib.load().fgnn_csr_split_length())
@@ -183,11 +192,7 @@ def csr_workspace(device, num_rows, max_edges, dim):
     per (device, bytes) like gat_workspace; the call expects nothing of its contents.  Calls that run concurrently on
     different streams need workspaces of their own."""
     nbytes = _lib.load().fgnn_csr_aggregate_workspace_bytes(num_rows, max_edges, dim)
-    key = (torch.device(device), nbytes)
-    ws = _CSR_WS.get(key)
-    if ws is None:
-        ws = _CSR_WS[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-    return ws, nbytes
+    return _csr_ws(device, nbytes), nbytes
 
 
 def csr_aggregate_into(out, h, indptr, indices, nodes=None, first=0, count=None, edge_weight=None, src_deg=None,
@@ -367,6 +372,55 @@ def gat_attention(feat, el, er, row, col, num_dst, negative_slope=0.2, attn_drop
     assert out.dtype == torch.float32 and out.shape == (num_dst, H, F) and out.is_contiguous()
     p = float(attn_drop) if training else 0.0
     return _GatAttention.apply(feat, el, er, out, row, col, float(negative_slope), p, int(seed), d_step, int(tag))
+
+
+# ---- GAT attention over whole CSR rows: exact layer-wise GAT inference (csrc/csr_gat_attention.hip) ---------------------
+
+def csr_gat_max_heads():
+    """heads the kernel's per-wave staging of the edge weights holds (fgnn_csr_gat_max_heads); more are refused"""
+    return int(_lib.load().fgnn_csr_gat_max_heads())
+
+
+def csr_gat_workspace(device, num_rows, max_edges, H, F):
+    """the scratch of fgnn_csr_gat_attention for these sizes on `device` (hub queue, piece descriptors, partial rows),
+    cached per (device, bytes) together with csr_workspace's; the call expects nothing of its contents.  Calls that run
+    concurrently on different streams need workspaces of their own."""
+    nbytes = _lib.load().fgnn_csr_gat_workspace_bytes(num_rows, max_edges, H, F)
+    return _csr_ws(device, nbytes), nbytes
+
+
+def csr_gat_attention_into(out, feat, el, er, indptr, indices, nodes=None, first=0, count=None, negative_slope=0.2,
+                           max_edges=None):
+    """out[i, h, :] = sum over v's CSR row of a[p, h] * feat[indices[p], h, :] with a[., h] = softmax over the row of
+    leaky_relu(el[indices[p], h] + er[v, h], negative_slope), for v = nodes[i], or v = first + i for i < count (default:
+    out's rows): fgnn_csr_gat_attention, no autograd, no dropout.  out [rows, H, F] (fp32) is OVERWRITTEN -- no zero
+    fill, rows without a neighbour become zeros --, feat is [N, H, F] fp32; both may be column blocks of wider row-major
+    matrices.  el and er are fp32 [N, H], one row per NODE (er too, unlike gat_forward_into's).  indptr / indices: the
+    int32-viewed u32 CSR tensors the engine uses.  No float atomics: a row's bits depend on the row alone, whatever
+    else the call computes.  H <= csr_gat_max_heads().  max_edges: upper bound of the summed lengths of the call's rows
+    (default: the graph's edge count, which holds unless `nodes` repeats ids; rows beyond the bound are still right,
+    only computed by one wave each)."""
+    assert _rows_ok(out) and _rows_ok(feat) and feat.shape[1:] == out.shape[1:]
+    N, H, F = feat.shape
+    assert el.dtype == torch.float32 and el.is_contiguous() and el.shape == (N, H)
+    assert er.dtype == torch.float32 and er.is_contiguous() and er.shape == (N, H)
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    if nodes is not None:
+        assert nodes.dtype == torch.int32 and nodes.is_contiguous() and count is None
+        count = nodes.numel()
+    elif count is None:
+        count = out.shape[0]
+    assert out.shape[0] >= count and (nodes is not None or first + count <= indptr.numel() - 1)
+    _lib._need_gpu(out, feat, el, er, indptr, indices, nodes)
+    if max_edges is None:
+        max_edges = indices.numel()
+    ws, nbytes = csr_gat_workspace(feat.device, count, max_edges, H, F)
+    code = _lib.load().fgnn_csr_gat_attention(_ptr(indptr), _ptr(indices), _ptr(nodes), first, count, max_edges, _ptr(el),
+                                              _ptr(er), _ptr(feat), feat.stride(0), H, F, negative_slope, _ptr(out),
+                                              out.stride(0), _ptr(ws), nbytes, _st(feat))
+    _lib._check(code, "fgnn_csr_gat_attention")
+    return out
 
 
 class _XentWs:

@@ -454,6 +454,32 @@ int fgnn_csr_aggregate_f16(const uint32_t *indptr, const uint32_t *indices, cons
                            size_t h_ld, size_t dim, float *out, size_t out_ld, const float *src_deg, int src_mode,
                            const float *dst_deg, int dst_mode, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- GAT attention over whole CSR rows (csrc/csr_gat_attention.hip; exact layer-wise GAT inference:
+ * examples/inference.py gat_layerwise_inference) ---------------------------------------------------------------------------
+ * num_head heads H of num_feat features F.  For output row i < num_rows, with v = nodes ? nodes[i] : first + i and the
+ * CSR range [indptr[v], indptr[v + 1]):
+ *   s[p, h] = leaky_relu(el[indices[p] * H + h] + er[v * H + h], negative_slope)
+ *   a[p, h] = softmax of s[., h] over the row
+ *   out[i * out_ld + h * F + f] = sum over p of a[p, h] * feat[indices[p] * feat_ld + h * F + f]
+ * el and er are fp32 [num_node, H], BOTH indexed by node id; feat and out are fp32 rows with a stride.  out is
+ * OVERWRITTEN; a row without a neighbour becomes zeros.  Inference only: no dropout, no alpha output, no gradient;
+ * residual, bias and activation are the caller's.  As fgnn_csr_aggregate: one wave owns an output row, no float atomics,
+ * rows of more than fgnn_csr_split_length() edges are cut into pieces that other waves compute into `ws` and that are
+ * combined in piece order (piece k: max m_k, sums z_k and acc_k of exp(s - m_k) in CSR order; row: m = max m_k, c_k =
+ * exp(m_k - m), out = sum c_k acc_k / sum c_k z_k), so a node's result is bit for bit the same whatever else a call
+ * computes; everything is enqueued on `stream` without a host synchronisation.  max_edges and ws as for
+ * fgnn_csr_aggregate, ws_bytes >= fgnn_csr_gat_workspace_bytes(num_rows, max_edges, num_head, num_feat).  num_rows == 0
+ * returns FGNN_OK and touches nothing.  FGNN_EINVAL before any launch: a null required pointer, a pointer that is not
+ * 4-byte aligned, num_head or num_feat 0, num_head > fgnn_csr_gat_max_heads() (the per-wave staging of the edge
+ * weights in LDS), a stride below H F, first + num_rows or max_edges beyond 2^32, a workspace that is too small or not
+ * 16-byte aligned. */
+size_t fgnn_csr_gat_max_heads(void);
+size_t fgnn_csr_gat_workspace_bytes(size_t num_rows, size_t max_edges, size_t num_head, size_t num_feat);
+int fgnn_csr_gat_attention(const uint32_t *indptr, const uint32_t *indices, const uint32_t *nodes, size_t first,
+                           size_t num_rows, size_t max_edges, const float *el, const float *er, const float *feat,
+                           size_t feat_ld, size_t num_head, size_t num_feat, float negative_slope, float *out,
+                           size_t out_ld, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- fused GAT layer: edge-softmax attention and its aggregation (csrc/gat_attention.hip; examples/models.py
  * FusedGATConv; reference: dgl.nn.GATConv of example/samgraph/train_gat.py) ------------------------------------------------
  * num_head heads H of num_feat features F each; feat / out / gout / gfeat are [rows, H, F] with a row stride (>= H F
