@@ -308,6 +308,7 @@ class HostTable:
         self.registered = False
         rc = self.hip.hipHostRegister(C.c_void_p(self.ptr), C.c_size_t(self.nbytes), C.c_uint(3))  # portable | mapped
         if rc != 0:
+            self.hip.hipGetLastError()  # a refused registration must not be reported by the caller's next kernel launch
             self.free()
             raise RuntimeError("hipHostRegister failed with %d" % rc)
         self.registered = True

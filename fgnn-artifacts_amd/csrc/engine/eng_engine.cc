@@ -79,10 +79,14 @@ Engine &Engine::Get() {
   return e;
 }
 
-static void *DeviceVisible(void *host) {
-  void *dev = nullptr;
-  SAM_HIP(hipHostGetDevicePointer(&dev, host, 0));
-  return dev;
+// The host feature table becomes GPU-readable: the shared table itself, registered, where the platform can do that --
+// one table for every trainer of the job.  Where it cannot (RegisterShared), this process reads its own pinned copy.
+void Engine::PinHostFeatures() {
+  if (RegisterShared(ds_.feat.ptr, ds_.feat.bytes, &dev_host_feat_)) return;
+  SAM_LOG(kWarning) << "host feature table: the platform does not register shared host memory; this process gathers "
+                    << "from a pinned copy of its own (" << ds_.feat.bytes << " bytes)";
+  SAM_HIP(hipHostMalloc(&dev_host_feat_, ds_.feat.bytes ? ds_.feat.bytes : 16, hipHostMallocPortable | hipHostMallocMapped));
+  memcpy(dev_host_feat_, ds_.feat.ptr, ds_.feat.bytes);
 }
 
 void Engine::Init() {
@@ -308,8 +312,7 @@ void Engine::InitInProcess() {
     SAM_HIP(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking));
     for (auto &e : x.ev) SAM_HIP(hipEventCreate(&e));
   }
-  SAM_HIP(hipHostRegister(ds_.feat.ptr, ds_.feat.bytes, hipHostRegisterPortable | hipHostRegisterMapped));
-  dev_host_feat_ = DeviceVisible(ds_.feat.ptr);
+  PinHostFeatures();
   SAM_HIP(hipMalloc(&d_label_, ds_.label.bytes));
   SAM_HIP(hipMemcpy(d_label_, ds_.label.ptr, ds_.label.bytes, hipMemcpyHostToDevice));
   if (RC().UseGPUCache()) BuildTrainerCache();
@@ -587,6 +590,28 @@ void Engine::PublishSlot(int slot) {
   sstat_.pub_wait += t_wait.Passed();
   Timer t_pub;
   SAM_CHECK_EQ(m.overflow, 0u) << "batch exceeded its buffers";
+  {
+    // what the pack kernel wrote into the host slot (pack.hip): the whole message, with the checksum behind it if it
+    // carries one -- or, with the arrays in a device-ring slot, the headers alone (one that does not fit: TransData only)
+    const bool use_cache = RC().UseGPUCache(), have_data = RC().sample_type == kRandomWalk;
+    size_t words = m.num_output;
+    if (!use_cache || RC().have_switcher) words += m.num_input;
+    if (use_cache) words += 2 * (size_t)m.num_input;
+    ByteRange r[1 + FGNN_MAX_LAYERS] = {{0, sizeof(TransData)}};
+    int n = 1;
+    size_t end = sizeof(TransData) + words * sizeof(uint32_t);
+    for (uint32_t l = 0; l < m.num_layers; ++l) {
+      r[n++] = ByteRange{end, sizeof(GraphData)};
+      end += sizeof(GraphData) + m.num_edge[l] * (have_data ? 3 : 2) * sizeof(uint32_t);
+    }
+    if (end > mq_->SlotBytes()) {
+      n = 1;
+    } else if (!s.mq_on_device) {
+      r[0].len = std::min(end + (s.mq_checked ? 2 * sizeof(uint32_t) : 0), mq_->SlotBytes());
+      n = 1;
+    }
+    mq_->FlushDeviceSlot(s.mq_key, r, n);
+  }
   mq_->SimpleSend(s.mq_key);
   // sample / cache-index times from the kernels' own time stamps in the summary (10 ns ticks): three event records and
   // their bubbles per batch less on the sampler's streams
@@ -694,9 +719,10 @@ void Engine::FinishBatch(int cur) {
   a.ship_input = (!use_cache || RC().have_switcher) ? 1 : 0;
   a.ship_cache_index = use_cache ? 1 : 0;
   a.have_data = RC().sample_type == kRandomWalk ? 1 : 0;
-  a.slot = DeviceVisible(slot);
+  a.slot = mq_->DeviceSlot(s.mq_key);
   // null: no device ring, or none of its slots is free (counted per sampler either way: samgraph_ext_queue_stats)
   a.payload = mq_->ClaimDeviceSlot(ring_id_ >= 0 ? ring_id_ : (RC().run_arch == kArch5 ? worker_id_ : 0), s.mq_key);
+  s.mq_on_device = a.payload != nullptr;
   a.slot_bytes = mq_->SlotBytes();
   a.h_meta = reinterpret_cast<uint32_t *>(fgnn_batch_host_meta(s.fb));
   const bool check = handoff_check_left_ > 0;
@@ -706,6 +732,7 @@ void Engine::FinishBatch(int cur) {
     a.msg_words = s.d_msg_words;
   }
   mq_->MarkChecked(s.mq_key, worker_id_, check);
+  s.mq_checked = check;
   SAM_FGNN(LaunchPack(a, s.st));
   if (check) {  // checksum of the packed words, appended behind them in the slot the payload went to
     uint32_t *where = static_cast<uint32_t *>(a.payload ? a.payload : a.slot);
@@ -761,8 +788,7 @@ void Engine::TrainInit(int worker_id, Context ctx, DistType type) {
   if (!second_half) mq_->PinMemory();
   // the host feature table becomes GPU-readable: miss rows are fetched by the gather kernel itself
   // (replaces the OpenMP ExtractMissData + H2D copy, cuda_cache_manager_host.cc:38-56)
-  SAM_HIP(hipHostRegister(ds_.feat.ptr, ds_.feat.bytes, hipHostRegisterPortable | hipHostRegisterMapped));
-  dev_host_feat_ = DeviceVisible(ds_.feat.ptr);
+  PinHostFeatures();
   SAM_HIP(hipMalloc(&d_label_, ds_.label.bytes));
   SAM_HIP(hipMemcpy(d_label_, ds_.label.ptr, ds_.label.bytes, hipMemcpyHostToDevice));
   if (RC().UseGPUCache()) {
@@ -869,7 +895,6 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
   bool payload_on_device = false;
   const char *payload = static_cast<const char *>(mq_->Payload(mq_key, msg, &payload_on_device));
   const uint32_t *p = reinterpret_cast<const uint32_t *>(msg + sizeof(TransData));
-  const ptrdiff_t to_payload = payload - msg;
   auto b = std::make_shared<GraphBatch>();
   x.b = b;
   x.mq_key = mq_key;
@@ -882,9 +907,9 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
   // Arrays that outlive the queue slot (ids, COO) go into ONE pooled buffer, copied by ONE kernel; the cache index
   // arrays are used in place by the gathers below (the slot is released only after they have run).  `in_place`
   // translates a position in the host slot into the device-visible address of the same position in the payload slot.
+  const char *dev_msg = payload;  // device-visible address of the payload slot (a host slot's: once its length is known)
   auto in_place = [&](const uint32_t *src) -> const uint32_t * {
-    const char *q = reinterpret_cast<const char *>(src) + to_payload;
-    return reinterpret_cast<const uint32_t *>(payload_on_device ? q : static_cast<const char *>(mq_->DeviceVisiblePtr(q)));
+    return reinterpret_cast<const uint32_t *>(dev_msg + (reinterpret_cast<const char *>(src) - msg));
   };
   constexpr size_t kAlignWords = 64;  // 256-byte aligned sub-arrays
   auto padded = [&](size_t n) { return (n + kAlignWords - 1) / kAlignWords * kAlignWords; };
@@ -898,6 +923,10 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
       keep_words += (hdr.have_data ? 3 : 2) * padded(g[2]);
       q += sizeof(GraphData) / sizeof(uint32_t) + g[2] * (hdr.have_data ? 3 : 2);
     }
+    size_t msg_bytes = (size_t)((const char *)q - msg);
+    SAM_CHECK_LE(msg_bytes, mq_->SlotBytes());
+    if (mq_->IsChecked(mq_key)) msg_bytes = std::min(msg_bytes + 2 * sizeof(uint32_t), mq_->SlotBytes());  // the checksum
+    if (!payload_on_device) dev_msg = static_cast<const char *>(mq_->DeviceView(mq_key, msg_bytes));
   }
   uint32_t *keep = static_cast<uint32_t *>(dev_pool_.Alloc(keep_words * sizeof(uint32_t)));
   b->pooled.push_back(keep);
@@ -962,8 +991,7 @@ void Engine::TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key) {
     // synchronisation costs nothing that is measured)
     if (!x.d_check) SAM_HIP(hipMalloc(&x.d_check, sizeof(uint32_t)));
     SAM_HIP(hipMemsetAsync(x.d_check, 0, sizeof(uint32_t), tstream_));
-    const char *base = payload_on_device ? payload : static_cast<const char *>(mq_->DeviceVisiblePtr(msg));
-    SAM_FGNN(LaunchMessageChecksum(reinterpret_cast<uint32_t *>(const_cast<char *>(base)), nullptr,
+    SAM_FGNN(LaunchMessageChecksum(reinterpret_cast<uint32_t *>(const_cast<char *>(dev_msg)), nullptr,
                                    (size_t)((const char *)p - msg) / sizeof(uint32_t), 1, x.d_check, tstream_));
     uint32_t bad = 0;
     SAM_HIP(hipMemcpyAsync(&bad, x.d_check, sizeof(bad), hipMemcpyDeviceToHost, tstream_));

@@ -165,6 +165,7 @@ class Engine {
   void TrainerIssue(ExtractCtx &x, const void *taken, size_t taken_key);
   void TrainerComplete(ExtractCtx &x);
   void BuildTrainerCache();
+  void PinHostFeatures();
 
   Dataset ds_;
   bool initialized_ = false, data_initialized_ = false;
@@ -205,7 +206,7 @@ class Engine {
   void *d_label_ = nullptr;
   uint32_t *d_cache_table_ = nullptr;  // direct-map table u32[num_node]
   void *d_cache_rows_ = nullptr;       // trainer: cached feature rows
-  void *dev_host_feat_ = nullptr;      // device-visible address of the registered host feature table
+  void *dev_host_feat_ = nullptr;      // device-visible address of the host feature table (PinHostFeatures)
   size_t num_cached_ = 0;
 
   fgnn_sampler *sampler_ = nullptr;
@@ -225,6 +226,7 @@ class Engine {
     // arch5: message being written
     bool pending = false;
     size_t mq_key = 0;
+    bool mq_on_device = false, mq_checked = false;  // its arrays went to a device-ring slot; it carries a checksum
     uint64_t key = 0;
     Timer started;
     uint64_t started_us = 0;  // SAMGRAPH_DUMP_TRACE: wall clock of the sample_once call

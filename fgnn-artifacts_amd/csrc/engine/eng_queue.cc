@@ -229,11 +229,71 @@ bool MemoryQueue::RingStats(int ring, uint64_t out[6]) const {
   return true;
 }
 
+bool RegisterShared(void *host, size_t bytes, void **dev) {
+  if (hipHostRegister(host, bytes, hipHostRegisterPortable | hipHostRegisterMapped) != hipSuccess) {
+    (void)hipGetLastError();  // or the next kernel launch of this thread reports it
+    return false;
+  }
+  SAM_HIP(hipHostGetDevicePointer(dev, host, 0));
+  return true;
+}
+
 void MemoryQueue::PinMemory() {
-  SAM_HIP(hipHostRegister(meta_, total_bytes_, hipHostRegisterPortable | hipHostRegisterMapped));
   void *d = nullptr;
-  SAM_HIP(hipHostGetDevicePointer(&d, meta_, 0));
-  dev_base_ = static_cast<const char *>(d);
+  if (RegisterShared(meta_, total_bytes_, &d)) {
+    dev_base_ = static_cast<char *>(d);
+    return;
+  }
+  SAM_LOG(kWarning) << "message queue: the platform does not register shared host memory; host-ring messages are staged "
+                    << "through pinned buffers of each process";
+}
+
+char *MemoryQueue::TakeStage(size_t key) {
+  std::lock_guard<std::mutex> lk(stage_mu_);
+  for (auto &s : stages_)
+    if (!s.busy) {
+      s.key = key;
+      s.busy = true;
+      return s.buf;
+    }
+  void *p = nullptr;
+  SAM_HIP(hipHostMalloc(&p, meta_->mq_nbytes, hipHostMallocPortable | hipHostMallocMapped));
+  stages_.push_back(Stage{static_cast<char *>(p), key, true});
+  return stages_.back().buf;
+}
+
+void MemoryQueue::DropStage(size_t key) {
+  std::lock_guard<std::mutex> lk(stage_mu_);
+  for (auto &s : stages_)
+    if (s.busy && s.key == key) s.busy = false;
+}
+
+void *MemoryQueue::DeviceSlot(size_t key) {
+  if (dev_base_) return dev_base_ + (HostSlot(key) - reinterpret_cast<char *>(meta_));
+  return TakeStage(key);
+}
+
+void MemoryQueue::FlushDeviceSlot(size_t key, const ByteRange *ranges, int n) {
+  if (dev_base_) return;
+  std::unique_lock<std::mutex> lk(stage_mu_);
+  const char *buf = nullptr;
+  for (auto &s : stages_)
+    if (s.busy && s.key == key) buf = s.buf;
+  lk.unlock();
+  SAM_CHECK(buf) << "message " << key << " has no staging buffer";
+  for (int i = 0; i < n; ++i) {
+    SAM_CHECK_LE(ranges[i].off + ranges[i].len, meta_->mq_nbytes);
+    memcpy(HostSlot(key) + ranges[i].off, buf + ranges[i].off, ranges[i].len);
+  }
+  DropStage(key);
+}
+
+const void *MemoryQueue::DeviceView(size_t key, size_t bytes) {
+  if (dev_base_) return dev_base_ + (HostSlot(key) - reinterpret_cast<char *>(meta_));
+  SAM_CHECK_LE(bytes, meta_->mq_nbytes);
+  char *buf = TakeStage(key);
+  memcpy(buf, HostSlot(key), bytes);
+  return buf;
 }
 
 // Hand-shakes by per-slot SEQUENCE numbers, not by the reference's per-slot semaphore pairs (memory_queue.cc:104-138):
@@ -306,6 +366,7 @@ bool MemoryQueue::TryRecv(const void **data, size_t *key) {
 }
 
 void MemoryQueue::Release(size_t key) {
+  if (!dev_base_) DropStage(key);  // (a message read from a device-ring slot had none)
   uint32_t &loc = meta_->payload_loc[key % meta_->max_size];
   if (loc) {  // hand the device slot back to its sampler
     RingInfo &r = meta_->rings[(loc >> 8) - 1];

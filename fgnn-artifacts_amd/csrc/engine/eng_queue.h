@@ -1,5 +1,6 @@
 // eng_queue.h -- sampler -> trainer hand-off: a lock-free MPMC ring of fixed-size slots in a
-// MAP_SHARED|MAP_ANONYMOUS host mapping, hipHostRegister'ed by every child after fork, with the
+// MAP_SHARED|MAP_ANONYMOUS host mapping, hipHostRegister'ed by every child after fork (where the platform cannot
+// register existing host memory the GPU reaches a slot through a pinned staging buffer, see PinMemory), with the
 // reference's send / receive counters (memory_queue.h:46-115, memory_queue.cc:33-138; per-slot sequence numbers where
 // the reference has semaphore pairs, see eng_queue.cc)
 // and the reference's wire format (task_queue.cc:68-88: TransData 40 B header, GraphData 24 B).
@@ -9,7 +10,9 @@
 // serialized message into the mapped slot, so the sampler never waits for a size.
 #pragma once
 #include <atomic>
+#include <mutex>
 #include <thread>
+#include <vector>
 
 #include <cstddef>
 #include <cstdint>
@@ -77,10 +80,22 @@ struct QueueMeta {                 // MQ_MetaData, memory_queue.h:65-115
   alignas(256) char data[0];
 };
 
+// Makes shared host memory GPU-readable and -writable in place: *dev = its device-visible address.  false (nothing
+// changed, no HIP error left behind): the platform does not register existing host memory -- virtual machines whose
+// GPU driver cannot pin pages it did not allocate; the caller then goes through memory from hipHostMalloc
+bool RegisterShared(void *host, size_t bytes, void **dev);
+
+struct ByteRange {
+  size_t off, len;
+};
+
 class MemoryQueue {
  public:
   MemoryQueue(size_t slot_bytes, size_t num_slots);  // in the parent, before fork
-  void PinMemory();                                  // in each child (memory_queue.cc:47-49)
+  // in each child (memory_queue.cc:47-49): registers the queue with the GPU.  Where that is refused (RegisterShared) the
+  // shared mapping stays host-only and the GPU sees a message through a pinned staging buffer of this process -- as
+  // many as it has messages in hand: DeviceSlot / FlushDeviceSlot on the sending side, DeviceView on the receiving side
+  void PinMemory();
   void *GetPtr(size_t *key);                         // claim a slot for writing (blocks while the ring is full)
   void SimpleSend(size_t key);                       // publish
   const void *Recv(size_t *key);                     // blocks until a message is available
@@ -112,10 +127,15 @@ class MemoryQueue {
   // slots claimed for sending and not yet claimed by a receiver -- NOT the number of receivable messages (a claimed
   // slot may still be waiting for its payload): use TryRecv to ask for a message without blocking
   size_t Pending() const { return *(volatile size_t *)&meta_->send_cnt - *(volatile size_t *)&meta_->recv_cnt; }
-  // device-visible address of a pointer into the (pinned) queue region, for kernels that read a host slot in place
-  const void *DeviceVisiblePtr(const void *host_ptr) const {
-    return dev_base_ + (static_cast<const char *>(host_ptr) - reinterpret_cast<const char *>(meta_));
-  }
+  // sender, between GetPtr and SimpleSend: the device-visible address of message `key`'s host slot, for the kernels
+  // that write it
+  void *DeviceSlot(size_t key);
+  // sender, once those kernels have finished and before SimpleSend: the byte ranges of the slot they wrote (a staged
+  // slot reaches the shared mapping here; nothing to do for a registered queue)
+  void FlushDeviceSlot(size_t key, const ByteRange *ranges, int n);
+  // receiver, between Recv and Release: the device-visible address of the first `bytes` bytes of message `key`'s host
+  // slot, for kernels that read them in place
+  const void *DeviceView(size_t key, size_t bytes);
 
   // ---- device ring (see RingInfo) ----
   // sampler process, after fork, current device = the sampler's: allocates `slots` message slots in HBM and exports
@@ -132,7 +152,19 @@ class MemoryQueue {
  private:
   QueueMeta *meta_;
   size_t total_bytes_;
-  const char *dev_base_ = nullptr;  // device-visible address of meta_ (set by PinMemory)
+  char *dev_base_ = nullptr;        // device-visible address of meta_ (set by PinMemory; null: staged)
+  char *HostSlot(size_t key) const { return meta_->data + (key % meta_->max_size) * meta_->mq_nbytes; }
+  // staging buffers (hipHostMalloc, one slot each) of the messages this process has in hand, when the queue could not be
+  // registered: taken by DeviceSlot / DeviceView, given back by FlushDeviceSlot / Release
+  struct Stage {
+    char *buf;
+    size_t key;
+    bool busy;
+  };
+  std::vector<Stage> stages_;
+  std::mutex stage_mu_;
+  char *TakeStage(size_t key);
+  void DropStage(size_t key);
   void ServiceSpills(int ring);
   void *local_slot_[kMaxRings][kMaxRingSlots] = {};   // slots of the rings this process owns
   void *mapped_slot_[kMaxRings][kMaxRingSlots] = {};  // slots of other processes' rings, opened through IPC on first use
