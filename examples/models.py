@@ -469,24 +469,27 @@ class FusedGATConv(GATConv):
         return self.finish(rst, h_dst, biased=True)
 
 
-class GAT(nn.Module):
-    """the reference's GAT (example/samgraph/train_gat.py): inner layers of `heads` heads with n_hidden // heads
-    features each, flattened (layer width n_hidden: 256 = 8 x 32), ELU; the last layer `out_heads` heads of n_classes,
-    averaged.  Feature dropout `dropout` and attention dropout `attn_drop` (default: the same) in every layer."""
+class _AttentionNet(nn.Module):
+    """what GAT and GATv2 share -- the reference's architecture (example/samgraph/train_gat.py): inner layers of `heads`
+    heads with n_hidden // heads features each, flattened (layer width n_hidden: 256 = 8 x 32), ELU; the last layer
+    `out_heads` heads of n_classes, averaged.  Feature dropout `dropout` and attention dropout `attn_drop` (default: the
+    same) in every layer.  `convs` = the (op by op, fused) layer classes."""
+
+    convs = None
 
     def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True, heads=8, out_heads=1,
-                 attn_drop=None, negative_slope=0.2, residual=False):
+                 attn_drop=None, negative_slope=0.2, residual=False, **conv_kw):
         super().__init__()
         assert n_hidden % heads == 0, "n_hidden must be a multiple of heads"
         attn_drop = dropout if attn_drop is None else attn_drop
-        conv = FusedGATConv if fused else GATConv
+        conv = self.convs[bool(fused)]
         self.fused = fused
         layers = []
         for i in range(n_layers):
             last = i == n_layers - 1
             layers.append(conv(in_feats if i == 0 else n_hidden, n_classes if last else n_hidden // heads,
                                out_heads if last else heads, dropout, attn_drop, negative_slope,
-                               residual and i > 0, None if last else F.elu))
+                               residual and i > 0, None if last else F.elu, **conv_kw))
         self.layers = nn.ModuleList(layers)
         # as SAGE / GCN: a training loop that uses fgnn_hip.nn.Adam sets dropout_step to its device-side step count, which
         # then keys the attention masks (a replayed graph draws a fresh mask per step).  Unset: every forward takes a fresh
@@ -507,6 +510,109 @@ class GAT(nn.Module):
             h = layer(block, h)
             h = h.mean(1) if i == len(self.layers) - 1 else h.flatten(1)
         return h
+
+
+class GAT(_AttentionNet):
+    """the reference's GAT: _AttentionNet on GATConv / FusedGATConv"""
+
+    convs = (GATConv, FusedGATConv)
+
+
+class GATv2Conv(nn.Module):
+    """dgl.nn.GATv2Conv on a block, op by op: the dynamic attention of "How Attentive are Graph Attention Networks?" --
+    two projections (`fc_src` for the sources, `fc_dst` for the destinations, both with a bias; share_weights=True drops
+    fc_dst and uses fc_src for both sides), the score attn . leaky_relu(fs[u] + fd[v]) per head, softmax over every
+    destination's incoming edges, attention dropout, the weighted sum of the fs rows, residual, activation.  The score
+    needs fs[row] + fd[col], an E x H x F tensor.  Parameter names and shapes are DGL's (fc_src.weight / .bias, fc_dst.weight
+    / .bias, attn [1, H, F], res_fc.weight when the residual needs a projection).  Returns [num_dst, H, F]."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False,
+                 activation=None, share_weights=False):
+        super().__init__()
+        self.in_feats, self.out_feats, self.num_heads = in_feats, out_feats, num_heads
+        self.fc_src = TallLinear(in_feats, out_feats * num_heads, bias=True)
+        self.fc_dst = None if share_weights else TallLinear(in_feats, out_feats * num_heads, bias=True)
+        self.attn = nn.Parameter(th.empty(1, num_heads, out_feats))
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.negative_slope = negative_slope
+        self.res_fc = None
+        if residual:
+            self.res_fc = (TallLinear(in_feats, out_feats * num_heads, bias=False) if in_feats != out_feats * num_heads
+                           else nn.Identity())
+        self.activation = activation
+        gain = nn.init.calculate_gain("relu")  # DGL's reset_parameters
+        for fc in (self.fc_src, self.fc_dst, self.res_fc):
+            if isinstance(fc, nn.Linear):
+                nn.init.xavier_normal_(fc.weight, gain=gain)
+                if fc.bias is not None:
+                    nn.init.zeros_(fc.bias)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+
+    def project(self, block, h):
+        """(h_dst after feature dropout, fs [num_src, H, F], fd [num_dst, H, F])"""
+        num_dst = block.number_of_dst_nodes()
+        h = self.feat_drop(h)
+        fs = self.fc_src(h).view(-1, self.num_heads, self.out_feats)
+        fd = fs[:num_dst] if self.fc_dst is None else self.fc_dst(h[:num_dst]).view(-1, self.num_heads, self.out_feats)
+        return h[:num_dst], fs, fd
+
+    def finish(self, rst, h_dst, residual_done=False):
+        if self.res_fc is not None and not residual_done:
+            rst = rst + self.res_fc(h_dst).view(h_dst.shape[0], -1, self.out_feats)
+        return self.activation(rst) if self.activation else rst
+
+    def forward(self, block, h):
+        num_dst = block.number_of_dst_nodes()
+        h_dst, fs, fd = self.project(block, h)
+        row, col = block.row.long(), block.col.long()
+        fsr = fs[row]
+        e = (F.leaky_relu(fsr + fd[col], self.negative_slope) * self.attn).sum(-1)  # [E, H]
+        m = th.full((num_dst, self.num_heads), float("-inf"), dtype=e.dtype, device=e.device)
+        m = m.scatter_reduce(0, col.unsqueeze(1).expand_as(e), e.detach(), reduce="amax", include_self=True)
+        p = th.exp(e - m[col])
+        z = th.zeros((num_dst, self.num_heads), dtype=e.dtype, device=e.device).index_add_(0, col, p)
+        a = self.attn_drop(p / z[col])
+        rst = th.zeros((num_dst, self.num_heads, self.out_feats), dtype=fs.dtype, device=fs.device)
+        rst = rst.index_add_(0, col, fsr * a.unsqueeze(-1))
+        return self.finish(rst, h_dst)
+
+
+class FusedGATv2Conv(GATv2Conv):
+    """GATv2Conv with everything between the projections and the activation as one autograd node on the kernels of
+    csrc/gatv2_attention.hip (fgnn_hip.nn.gatv2_attention): no E x H x F tensor is written in either direction.  The
+    residual is pre-filled into the node's output.  Same parameters under the same names; off the GPU / without the HIP
+    library / for other dtypes it IS GATv2Conv.  `dropout_key` as FusedGATConv's."""
+
+    dropout_key = (0x5A4D47, None, 0)
+
+    def forward(self, block, h):
+        if not _fused_layers_apply(block, h):
+            return super().forward(block, h)
+        from fgnn_hip.nn import gatv2_attention
+        num_dst = block.number_of_dst_nodes()
+        h_dst, fs, fd = self.project(block, h)
+        out = None
+        if self.res_fc is not None:
+            out = self.res_fc(h_dst).reshape(num_dst, self.num_heads, self.out_feats)
+            out = out.clone() if isinstance(self.res_fc, nn.Identity) else out  # the node writes into it
+        seed, d_step, tag = self.dropout_key
+        rst = gatv2_attention(fs, fd, self.attn, block.row, block.col, num_dst, self.negative_slope, self.attn_drop.p,
+                              self.training, seed, d_step, tag, out=out)
+        return self.finish(rst, h_dst, residual_done=True)
+
+
+class GATv2(_AttentionNet):
+    """GAT's architecture and constructor (heads, widths, dropouts, the `fused=` switch, the dropout_seed / dropout_step
+    handling) on GATv2 layers; a class of its own, not a GAT: what dispatches on GAT (examples/inference.py) must not
+    take it for one"""
+
+    convs = (GATv2Conv, FusedGATv2Conv)
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True, heads=8, out_heads=1,
+                 attn_drop=None, negative_slope=0.2, residual=False, share_weights=False):
+        super().__init__(in_feats, n_hidden, n_classes, n_layers, dropout, fused, heads, out_heads, attn_drop,
+                         negative_slope, residual, share_weights=share_weights)
 
 
 class SAGE(nn.Module):
@@ -585,4 +691,4 @@ class PinSAGE(nn.Module):
         return h
 
 
-MODELS = {"graphsage": SAGE, "gcn": GCN, "pinsage": PinSAGE, "gat": GAT}
+MODELS = {"graphsage": SAGE, "gcn": GCN, "pinsage": PinSAGE, "gat": GAT, "gatv2": GATv2}

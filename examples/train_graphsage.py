@@ -70,8 +70,8 @@ def main():
                          "inference over the full graph) to FILE.npy")
     ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
     # GAT (example/samgraph/train_gat.py: 8 heads x 32 hidden, attention dropout = feature dropout)
-    ap.add_argument("--num-heads", type=int, default=8, help="gat: attention heads of the inner layers")
-    ap.add_argument("--attn-drop", type=float, default=None, help="gat: attention dropout (default: --dropout)")
+    ap.add_argument("--num-heads", type=int, default=8, help="gat / gatv2: attention heads of the inner layers")
+    ap.add_argument("--attn-drop", type=float, default=None, help="gat / gatv2: attention dropout (default: --dropout)")
     ap.add_argument("--feat-store", default="f32", choices=["f32", "f16"],
                     help="f16: the engine keeps, caches and gathers the input features as IEEE binary16 rows "
                          "(config key feat_store_dtype; feat_f16.bin, written by --make-dataset or by `fgnn_dataset "
@@ -120,7 +120,7 @@ def main():
         sam.start()
     dev = th.device(trainer_ctx)
     num_layer = args.num_layer if args.model == "pinsage" else len(args.fanout)
-    kw = dict(heads=args.num_heads, attn_drop=args.attn_drop) if args.model == "gat" else {}
+    kw = dict(heads=args.num_heads, attn_drop=args.attn_drop) if args.model in ("gat", "gatv2") else {}
     model = MODELS[args.model](sam.feat_dim(), args.num_hidden, sam.num_class(), num_layer, args.dropout,
                                fused=not args.op_by_op, **kw).to(dev)
     get_blocks = sam.get_dgl_blocks_with_weights if args.model == "pinsage" else sam.get_dgl_blocks

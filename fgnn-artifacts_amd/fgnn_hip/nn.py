@@ -374,6 +374,118 @@ def gat_attention(feat, el, er, row, col, num_dst, negative_slope=0.2, attn_drop
     return _GatAttention.apply(feat, el, er, out, row, col, float(negative_slope), p, int(seed), d_step, int(tag))
 
 
+# ---- fused GATv2 layer: dynamic attention, score and gradient kernels (csrc/gatv2_attention.hip) ---------------------------
+
+_GATV2_WS = {}
+
+
+def gatv2_workspace(device, num_edge, num_dst, num_head):
+    """the scratch of fgnn_gatv2_forward / fgnn_gatv2_backward, cached per (device, sizes) like gat_workspace: call it
+    BEFORE a graph capture whose first gatv2_attention call would otherwise allocate it inside the capture"""
+    key = (torch.device(device), num_edge, num_dst, num_head)
+    ws = _GATV2_WS.get(key)
+    if ws is None:
+        nbytes = _lib.load().fgnn_gatv2_workspace_bytes(num_edge, num_dst, num_head)
+        ws = _GATV2_WS[key] = torch.empty(max((nbytes + 3) // 4, 1), dtype=torch.float32, device=device)
+    return ws
+
+
+def _gatv2_check(fs, fd, attn, row, col):
+    assert _rows_ok(fs) and _rows_ok(fd) and fs.shape[1:] == fd.shape[1:]
+    assert attn.dtype == torch.float32 and attn.is_contiguous() and attn.numel() == fs.shape[1] * fs.shape[2]
+    assert row.dtype == torch.int32 and col.dtype == torch.int32 and row.is_contiguous() and col.is_contiguous()
+    assert row.numel() == col.numel()
+
+
+def gatv2_forward_into(out, alpha, fs, fd, attn, row, col, negative_slope=0.2, attn_p=0.0, seed=0, d_step=None, tag=0):
+    """fgnn_gatv2_forward, no autograd: alpha [E, H] is written, the attention-weighted sums of fs rows are ADDED to the
+    caller-initialised out [num_dst, H, F].  fs [num_src, H, F], fd [num_dst, H, F] and out may be column blocks of wider
+    matrices; attn holds H F contiguous values."""
+    num_dst, H, F = out.shape
+    _gatv2_check(fs, fd, attn, row, col)
+    assert _rows_ok(out) and fd.shape == out.shape
+    assert alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.shape == (row.numel(), H)
+    E = row.numel()
+    ws = gatv2_workspace(fs.device, E, num_dst, H)
+    _lib._check(_lib.load().fgnn_gatv2_forward(_ptr(row), _ptr(col), E, _ptr(fs), fs.stride(0), _ptr(fd), fd.stride(0),
+                                               _ptr(attn), num_dst, H, F, negative_slope, attn_p, seed, _ptr(d_step), tag,
+                                               _ptr(alpha), _ptr(out), out.stride(0), _ptr(ws), ws.numel() * 4, _st(fs)),
+                "fgnn_gatv2_forward")
+    return out
+
+
+def gatv2_backward_into(gfs, gfd, gattn, gout, alpha, fs, fd, attn, row, col, negative_slope=0.2, attn_p=0.0, seed=0,
+                        d_step=None, tag=0):
+    """fgnn_gatv2_backward, no autograd: the gradients are ADDED to the caller-initialised gfs [num_src, H, F], gfd
+    [num_dst, H, F] and gattn (H F contiguous values); each may be None and is then skipped.  The dropout key is the
+    forward call's."""
+    num_dst, H, F = gout.shape
+    _gatv2_check(fs, fd, attn, row, col)
+    assert _rows_ok(gout) and fd.shape == gout.shape
+    assert gfs is None or (_rows_ok(gfs) and gfs.shape == fs.shape)
+    assert gfd is None or (_rows_ok(gfd) and gfd.shape == fd.shape)
+    assert gattn is None or (gattn.dtype == torch.float32 and gattn.is_contiguous() and gattn.numel() == H * F)
+    assert alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.shape == (row.numel(), H)
+    E = row.numel()
+    ws = gatv2_workspace(fs.device, E, num_dst, H)
+    _lib._check(_lib.load().fgnn_gatv2_backward(_ptr(row), _ptr(col), E, _ptr(fs), fs.stride(0), _ptr(fd), fd.stride(0),
+                                                _ptr(attn), _ptr(alpha), _ptr(gout), gout.stride(0), num_dst, H, F,
+                                                negative_slope, attn_p, seed, _ptr(d_step), tag, _ptr(gfs),
+                                                gfs.stride(0) if gfs is not None else 0, _ptr(gfd),
+                                                gfd.stride(0) if gfd is not None else 0, _ptr(gattn), _ptr(ws),
+                                                ws.numel() * 4, _st(fs)), "fgnn_gatv2_backward")
+
+
+class _Gatv2Attention(torch.autograd.Function):
+    """`out` is the first input: where it is a view (of a residual projection's output, say), autograd rebases the view's
+    history on this node and takes the node's first gradient for the tensor modified in place"""
+
+    @staticmethod
+    def forward(ctx, out, fs, fd, attn, row, col, slope, attn_p, seed, d_step, tag):
+        fs, fd = (t if _rows_ok(t) else t.contiguous() for t in (fs, fd))
+        attn = attn.contiguous()
+        ctx.mark_dirty(out)
+        alpha = torch.empty((row.numel(), fs.shape[1]), dtype=torch.float32, device=fs.device)
+        gatv2_forward_into(out, alpha, fs, fd, attn, row, col, slope, attn_p, seed, d_step, tag)
+        ctx.save_for_backward(fs, fd, attn, alpha, row, col)
+        ctx.key = (slope, attn_p, seed, d_step, tag)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        fs, fd, attn, alpha, row, col = ctx.saved_tensors
+        if not _rows_ok(gout):
+            gout = gout.contiguous()
+        want = ctx.needs_input_grad
+        gfs, gfd, gattn = (torch.zeros_like(t, memory_format=torch.contiguous_format) if w else None
+                           for t, w in zip((fs, fd, attn), want[1:4]))
+        if any(want[1:4]):
+            gatv2_backward_into(gfs, gfd, gattn, gout, alpha, fs, fd, attn, row, col, *ctx.key)
+        return (gout if want[0] else None), gfs, gfd, gattn, None, None, None, None, None, None, None
+
+
+def gatv2_attention(fs, fd, attn, row, col, num_dst, negative_slope=0.2, attn_drop=0.0, training=False, seed=0x5A4D47,
+                    d_step=None, tag=0, out=None):
+    """GATv2's message passing on a block as one autograd node, differentiable in fs, fd and attn:
+        s[e, h] = sum_f attn[h, f] * leaky_relu(fs[row[e], h, f] + fd[col[e], h, f], negative_slope)
+        a = edge_softmax(s) per destination and head
+        out[col[e], h, :] += dropout(a, attn_drop)[e, h] * fs[row[e], h, :]
+    fs fp32 [num_src, H, F], fd [num_dst, H, F], attn [H, F] (or [1, H, F]), row / col int32 [E].  `out`, the dropout
+    mask and the workspace follow gat_attention's contract."""
+    assert fs.is_cuda and fs.dtype == torch.float32 and fs.dim() == 3
+    H, F = fs.shape[1], fs.shape[2]
+    assert fd.dtype == torch.float32 and fd.shape == (num_dst, H, F)
+    assert attn.dtype == torch.float32 and attn.numel() == H * F
+    assert row.dtype == torch.int32 and col.dtype == torch.int32
+    assert row.is_contiguous() and col.is_contiguous() and row.numel() == col.numel()
+    assert 0.0 <= attn_drop < 1.0
+    if out is None:
+        out = torch.zeros((num_dst, H, F), dtype=torch.float32, device=fs.device)
+    assert out.dtype == torch.float32 and out.shape == (num_dst, H, F) and out.is_contiguous()
+    p = float(attn_drop) if training else 0.0
+    return _Gatv2Attention.apply(out, fs, fd, attn, row, col, float(negative_slope), p, int(seed), d_step, int(tag))
+
+
 # ---- GAT attention over whole CSR rows: exact layer-wise GAT inference (csrc/csr_gat_attention.hip) ---------------------
 
 def csr_gat_max_heads():

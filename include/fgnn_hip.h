@@ -516,6 +516,37 @@ int fgnn_gat_backward(const uint32_t *src_index, const uint32_t *dst_index, size
                       float attn_p, uint64_t seed, const unsigned long long *d_step, uint32_t tag, float *gfeat,
                       size_t gfeat_ld, float *gel, float *ger, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- fused GATv2 layer: dynamic attention (csrc/gatv2_attention.hip; examples/models.py FusedGATv2Conv; the layer:
+ * dgl.nn.GATv2Conv) --------------------------------------------------------------------------------------------------------
+ * fs [num_src, H, F] and fd [num_dst, H, F] are the two projections, attn [H, F] the attention vector; fs / fd / out /
+ * gout / gfs / gfd have a row stride (>= H F elements), alpha is [num_edge, H], all fp32 and 4-byte aligned.
+ *   s[e,h] = sum over f of attn[h,f] * leaky_relu(fs[src_index[e],h,f] + fd[dst_index[e],h,f], negative_slope)
+ *   alpha, a~ as for fgnn_gat_forward (same softmax, same Philox keying of the dropout mask)
+ *   out[dst_index[e],h,:] += a~[e,h] * fs[src_index[e],h,:]
+ * Any F is served.  The segment sums behind alpha and the gattn sums are kept in double (in the workspace, which is
+ * therefore 8-byte aligned): a run's results do not depend on the order of those atomics.  The contract is fgnn_gat_forward's: any edge order, nothing of size num_edge x H x F is written, no
+ * host synchronisation, no allocation, num_edge == 0 returns FGNN_OK and touches nothing.  FGNN_EINVAL before any
+ * launch: a null required pointer, num_head or num_feat 0, a row stride below H F, a pointer that is not 4-byte
+ * aligned (ws: 8-byte), attn_p outside [0, 1), ws_bytes below fgnn_gatv2_workspace_bytes(num_edge, num_dst, num_head). */
+size_t fgnn_gatv2_workspace_bytes(size_t num_edge, size_t num_dst, size_t num_head);
+int fgnn_gatv2_forward(const uint32_t *src_index, const uint32_t *dst_index, size_t num_edge, const float *fs,
+                       size_t fs_ld, const float *fd, size_t fd_ld, const float *attn, size_t num_dst, size_t num_head,
+                       size_t num_feat, float negative_slope, float attn_p, uint64_t seed,
+                       const unsigned long long *d_step, uint32_t tag, float *alpha, float *out, size_t out_ld, void *ws,
+                       size_t ws_bytes, void *stream);
+/* With g = gout, u = fs[src_index[e]] + fd[dst_index[e]], the forward call's dropout key and gs as for
+ * fgnn_gat_backward (ga = <g[dst_index[e],h,:], fs[src_index[e],h,:]> keep / (1 - attn_p)):
+ *   gfs[src_index[e],h,f] += gs[e,h] attn[h,f] lrelu'(u) + a~[e,h] g[dst_index[e],h,f]
+ *   gfd[dst_index[e],h,f] += gs[e,h] attn[h,f] lrelu'(u)          lrelu'(u) = u > 0 ? 1 : negative_slope
+ *   gattn[h,f]            += gs[e,h] leaky_relu(u)
+ * gfs, gfd and gattn are caller-initialised accumulators; each may be NULL and is then skipped. */
+int fgnn_gatv2_backward(const uint32_t *src_index, const uint32_t *dst_index, size_t num_edge, const float *fs,
+                        size_t fs_ld, const float *fd, size_t fd_ld, const float *attn, const float *alpha,
+                        const float *gout, size_t gout_ld, size_t num_dst, size_t num_head, size_t num_feat,
+                        float negative_slope, float attn_p, uint64_t seed, const unsigned long long *d_step,
+                        uint32_t tag, float *gfs, size_t gfs_ld, float *gfd, size_t gfd_ld, float *gattn, void *ws,
+                        size_t ws_bytes, void *stream);
+
 /* ---- fused pieces of a GraphSAGE training step (consumer side, csrc/train_ops.hip) ----------------------------------
  * Elementwise work a training step otherwise does with two to four framework ops each; one launch apiece because the
  * step is replayed as a captured HIP graph, where every node costs the GPU 15-20 us whatever it does.  fp32, the same

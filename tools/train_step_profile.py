@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where does a training step (the layers of examples/models.py on the engine's COO blocks) spend GPU time?
-Default (--model graphsage): synthetic blocks of the papers100M-shaped batch size.  --model gcn / pinsage / gat: the blocks
+Default (--model graphsage): synthetic blocks of the papers100M-shaped batch size.  --model gcn / pinsage / gat / gatv2: the blocks
 of one real batch of bench.py's twitter / uk-2006-05 / products workload (same graph, train set and sampler), the op-by-op and the
 fused model stepped in alternation in this process (--ab alternations of --ab-steps steps, medians and spread per
 model), then the per-kernel table of the --fused one.  Profiling aid."""
@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "fgnn-artifacts_amd"))
 from models import MODELS, SAGE  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--model", default="graphsage", choices=["graphsage", "gcn", "pinsage", "gat"])
+ap.add_argument("--model", default="graphsage", choices=list(MODELS))
 ap.add_argument("--fused", type=int, default=None, choices=[0, 1],
                 help="the fused layers (1) or the op-by-op ones (0); default 1 (graphsage: SAGE_FUSED)")
 ap.add_argument("--ab", type=int, default=5, help="gcn / pinsage: alternations of the op-by-op and the fused model")
@@ -78,7 +78,7 @@ def ab_main():
     from fgnn_hip.nn import Adam, softmax_xent
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    workload = args.workload or {"gcn": "twitter", "pinsage": "uk-2006-05", "gat": "products"}[args.model]
+    workload = args.workload or {"gcn": "twitter", "pinsage": "uk-2006-05", "gat": "products", "gatv2": "products"}[args.model]
     blocks, w = real_batch_blocks(workload, dev)
     print("%s batch of %s: %s" % (args.model, workload, ", ".join(
         "%d src -> %d dst, %d edges" % (b.nsrc, b.ndst, b.row.numel()) for b in blocks)))
@@ -149,7 +149,7 @@ def feat_store_main():
     dev = "cuda:0"
     torch.cuda.set_device(0)
     workload = args.workload or {"graphsage": "papers100M", "gcn": "twitter", "pinsage": "uk-2006-05",
-                                 "gat": "products"}[args.model]
+                                 "gat": "products", "gatv2": "products"}[args.model]
     blocks, w = real_batch_blocks(workload, dev)
     b0 = blocks[0]
     print("%s batch of %s: %s" % (args.model, workload, ", ".join(
