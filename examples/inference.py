@@ -17,10 +17,17 @@ GAT has a pass of its own, gat_layerwise_inference: an edge-softmax over CSR row
 projects all N rows in chunks (feat = fc(h) as [N, H, F], el, er), then per chunk of destination rows runs
 fgnn_csr_gat_attention (csrc/csr_gat_attention.hip; fgnn_hip.nn.csr_gat_attention_into: one wave per CSR row, max, sum
 and weighted sums in registers, no E x H scratch, no float atomics, bit-reproducible rows) and the layer's own finish
-(residual, bias, ELU).  full_graph_inference picks the pass by the model's class; it is what the training scripts call.
+(residual, bias, ELU).
+
+GATv2 has gatv2_layerwise_inference, the same pass on its own kernel: the score attn . leaky_relu(fs[u] + fd[v]) is a
+reduction over the neighbour's whole projected row, so fgnn_csr_gatv2_attention (csrc/csr_gatv2_attention.hip;
+fgnn_hip.nn.csr_gatv2_attention_into) walks a CSR row ONCE with an online softmax in fixed blocks -- every fs row is read
+once, same guarantees.  full_graph_inference picks the pass by the model's class; it is what the training scripts call.
 
 Not built: PinSAGE (its neighbourhood is defined by random walks, not by the CSR) raises NotImplementedError;
 intermediate activations in fp16; inference partitioned over several GPUs."""
+import types
+
 import numpy as np
 import torch as th
 import torch.nn.functional as F
@@ -165,21 +172,113 @@ def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=N
     return h
 
 
-def _gat_chunk_op_by_op(feat, el, er, indptr64, indices64, a, b, slope):
-    """the attention sums [b - a, H, F] of the destination rows [a, b) with torch ops, as models.GATConv.forward computes
-    them on a block: scores, per-(destination, head) max, exp, sum, weighted sum; rows without a neighbour stay zero"""
+def _chunk_edges(indptr64, indices64, a, b):
+    """(src, dst) of the edges of the destination rows [a, b): the neighbour ids and the row's position in the chunk"""
     p0, p1 = int(indptr64[a]), int(indptr64[b])
-    src = indices64[p0:p1]
     k = indptr64[a + 1:b + 1] - indptr64[a:b]
-    dst = th.repeat_interleave(th.arange(b - a, device=feat.device), k)
-    e = F.leaky_relu(el[src] + er[a:b][dst], slope)
-    m = th.full((b - a, e.shape[1]), float("-inf"), dtype=e.dtype, device=e.device)
+    return indices64[p0:p1], th.repeat_interleave(th.arange(b - a, device=indptr64.device), k)
+
+
+def _edge_softmax_sum(e, msg, dst, rows):
+    """[rows, H, F]: the sums of msg [E, H, F] weighted by the softmax of the scores e [E, H] over every destination's
+    edges, as the op-by-op layers of models.py compute them on a block: per-(destination, head) max, exp, sum, weighted
+    sum; rows without a neighbour stay zero"""
+    m = th.full((rows, e.shape[1]), float("-inf"), dtype=e.dtype, device=e.device)
     m = m.scatter_reduce(0, dst.unsqueeze(1).expand_as(e), e, reduce="amax", include_self=True)
     p = th.exp(e - m[dst])
     z = th.zeros_like(m).index_add_(0, dst, p)
     alpha = p / z[dst]
-    rst = th.zeros((b - a,) + tuple(feat.shape[1:]), dtype=feat.dtype, device=feat.device)
-    return rst.index_add_(0, dst, feat[src] * alpha.unsqueeze(-1))
+    rst = th.zeros((rows,) + tuple(msg.shape[1:]), dtype=msg.dtype, device=msg.device)
+    return rst.index_add_(0, dst, msg * alpha.unsqueeze(-1))
+
+
+def _gat_chunk_op_by_op(feat, el, er, indptr64, indices64, a, b, slope):
+    """the attention sums [b - a, H, F] of the destination rows [a, b) with torch ops, as models.GATConv.forward computes
+    them on a block"""
+    src, dst = _chunk_edges(indptr64, indices64, a, b)
+    return _edge_softmax_sum(F.leaky_relu(el[src] + er[a:b][dst], slope), feat[src], dst, b - a)
+
+
+def _gatv2_chunk_op_by_op(fs, fd, attn, indptr64, indices64, a, b, slope):
+    """the same for models.GATv2Conv.forward: the score is attn . leaky_relu(fs[u] + fd[v]), an E x H x F tensor per
+    chunk"""
+    src, dst = _chunk_edges(indptr64, indices64, a, b)
+    fsr = fs[src]
+    return _edge_softmax_sum((F.leaky_relu(fsr + fd[a:b][dst], slope) * attn).sum(-1), fsr, dst, b - a)
+
+
+def _attention_inference(model, indptr, indices, feat, batch_rows, device, project):
+    """What the GAT and the GATv2 pass share.  Per layer `project(g, layer, h)` projects all N rows of h in g.chunks and
+    returns attend(a, b), the attention sums [b - a, H, F] of the destination rows [a, b); then per chunk the layer's
+    finish (residual from h[a:b], and what else the layer adds), flatten(1) between layers, mean(1) over the heads of
+    the last.  g: the graph on the device (indptr, indices; indptr64, indices64 for torch indexing), n, chunks, dtype,
+    device, max_edges of a chunk, and nn = fgnn_hip.nn where the kernels apply (GPU tensors, fp32 model, library
+    loadable), else None."""
+    g = types.SimpleNamespace()
+    g.device, g.dtype, g.indptr, g.indices, h, g.n = _on_device(model, indptr, indices, feat, device)
+    assert batch_rows >= 1
+    g.nn = _library() if g.device.type == "cuda" and g.dtype == th.float32 else None
+    was_training = model.training
+    model.eval()
+    try:
+        with th.no_grad():
+            g.indptr64 = _u32(g.indptr)
+            g.indices64 = _u32(g.indices)
+            g.max_edges = _longest_chunk(g.indptr64, g.n, batch_rows, g.device) if g.nn else 0
+            g.chunks = [(a, min(a + batch_rows, g.n)) for a in range(0, g.n, batch_rows)]
+            for li, layer in enumerate(model.layers):
+                H, Fo = layer.num_heads, layer.out_feats
+                attend = project(g, layer, h)
+                last = li == len(model.layers) - 1
+                out = th.empty((g.n, Fo if last else H * Fo), dtype=g.dtype, device=g.device)
+                for a, b in g.chunks:
+                    rst = layer.finish(attend(a, b), h[a:b].to(g.dtype))
+                    out[a:b] = rst.mean(1) if last else rst.flatten(1)
+                h = out
+    finally:
+        model.train(was_training)
+    return h
+
+
+def _gat_project(g, layer, h):
+    H, Fo = layer.num_heads, layer.out_feats
+    kernel = g.nn is not None and H <= g.nn.csr_gat_max_heads()
+    proj = th.empty((g.n, H, Fo), dtype=g.dtype, device=g.device)
+    el, er = (th.empty((g.n, H), dtype=g.dtype, device=g.device) for _ in range(2))
+    for a, b in g.chunks:
+        f = layer.fc(h[a:b].to(g.dtype)).view(b - a, H, Fo)
+        proj[a:b] = f
+        th.sum(f * layer.attn_l, -1, out=el[a:b])
+        th.sum(f * layer.attn_r, -1, out=er[a:b])
+
+    def attend(a, b):
+        if not kernel:
+            return _gat_chunk_op_by_op(proj, el, er, g.indptr64, g.indices64, a, b, layer.negative_slope)
+        rst = th.empty((b - a, H, Fo), dtype=th.float32, device=g.device)
+        return g.nn.csr_gat_attention_into(rst, proj, el, er, g.indptr, g.indices, first=a, count=b - a,
+                                           negative_slope=layer.negative_slope, max_edges=g.max_edges)
+    return attend
+
+
+def _gatv2_project(g, layer, h):
+    H, Fo = layer.num_heads, layer.out_feats
+    kernel = g.nn is not None and Fo <= g.nn.csr_gatv2_max_feats()
+    fs = th.empty((g.n, H, Fo), dtype=g.dtype, device=g.device)
+    fd = fs if layer.fc_dst is None else th.empty_like(fs)
+    for a, b in g.chunks:
+        x = h[a:b].to(g.dtype)
+        fs[a:b] = layer.fc_src(x).view(b - a, H, Fo)
+        if layer.fc_dst is not None:
+            fd[a:b] = layer.fc_dst(x).view(b - a, H, Fo)
+    attn = layer.attn.detach().contiguous()
+
+    def attend(a, b):
+        if not kernel:
+            return _gatv2_chunk_op_by_op(fs, fd, attn, g.indptr64, g.indices64, a, b, layer.negative_slope)
+        rst = th.empty((b - a, H, Fo), dtype=th.float32, device=g.device)
+        return g.nn.csr_gatv2_attention_into(rst, fs, fd, attn, g.indptr, g.indices, first=a, count=b - a,
+                                             negative_slope=layer.negative_slope, max_edges=g.max_edges)
+    return attend
 
 
 def gat_layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=None):
@@ -192,46 +291,26 @@ def gat_layerwise_inference(model, indptr, indices, feat, batch_rows=65536, devi
     bias, ELU; flatten(1) between layers, mean(1) over the heads of the last."""
     if not isinstance(model, models.GAT):
         raise NotImplementedError("gat_layerwise_inference knows models.GAT, not %s" % type(model).__name__)
-    device, dtype, indptr, indices, h, n = _on_device(model, indptr, indices, feat, device)
-    assert batch_rows >= 1
-    nn = _library() if device.type == "cuda" and dtype == th.float32 else None
-    was_training = model.training
-    model.eval()
-    try:
-        with th.no_grad():
-            indptr64 = _u32(indptr)
-            indices64 = _u32(indices)
-            max_edges = _longest_chunk(indptr64, n, batch_rows, device) if nn else 0
-            chunks = [(a, min(a + batch_rows, n)) for a in range(0, n, batch_rows)]
-            for li, layer in enumerate(model.layers):
-                H, Fo = layer.num_heads, layer.out_feats
-                kernel = nn is not None and H <= nn.csr_gat_max_heads()
-                proj = th.empty((n, H, Fo), dtype=dtype, device=device)
-                el, er = (th.empty((n, H), dtype=dtype, device=device) for _ in range(2))
-                for a, b in chunks:
-                    f = layer.fc(h[a:b].to(dtype)).view(b - a, H, Fo)
-                    proj[a:b] = f
-                    th.sum(f * layer.attn_l, -1, out=el[a:b])
-                    th.sum(f * layer.attn_r, -1, out=er[a:b])
-                last = li == len(model.layers) - 1
-                out = th.empty((n, Fo if last else H * Fo), dtype=dtype, device=device)
-                for a, b in chunks:
-                    if kernel:
-                        rst = th.empty((b - a, H, Fo), dtype=th.float32, device=device)
-                        nn.csr_gat_attention_into(rst, proj, el, er, indptr, indices, first=a, count=b - a,
-                                                  negative_slope=layer.negative_slope, max_edges=max_edges)
-                    else:
-                        rst = _gat_chunk_op_by_op(proj, el, er, indptr64, indices64, a, b, layer.negative_slope)
-                    rst = layer.finish(rst, h[a:b].to(dtype))
-                    out[a:b] = rst.mean(1) if last else rst.flatten(1)
-                h = out
-    finally:
-        model.train(was_training)
-    return h
+    return _attention_inference(model, indptr, indices, feat, batch_rows, device, _gat_project)
+
+
+def gatv2_layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=None):
+    """[N, n_classes] logits of `model` (models.GATv2, fused or op-by-op layers, with or without residual and
+    share_weights) for every node of the graph; arguments and conventions as gat_layerwise_inference.  Per layer: fs =
+    fc_src(h) [N, H, F] and fd = fc_dst(h) (fd is fs where the layer shares its weights) for all N rows in chunks of
+    batch_rows; then per chunk of destination rows the attention sums over their whole CSR rows -- on the GPU with an
+    fp32 model fgnn_hip.nn.csr_gatv2_attention_into (every fs row read once), else (CPU tensors, no kernel library,
+    float64, more features per head than the kernel serves) torch ops -- and the layer's finish: residual from h[a:b],
+    ELU; flatten(1) between layers, mean(1) over the heads of the last."""
+    if not isinstance(model, models.GATv2):
+        raise NotImplementedError("gatv2_layerwise_inference knows models.GATv2, not %s" % type(model).__name__)
+    return _attention_inference(model, indptr, indices, feat, batch_rows, device, _gatv2_project)
 
 
 def full_graph_inference(model, indptr, indices, feat, batch_rows=65536, device=None):
     """the exact prediction of `model` for every node by the pass its class has: gat_layerwise_inference for models.GAT,
-    layerwise_inference for everything else (which refuses what it cannot do, models.PinSAGE, with a reason)"""
-    fn = gat_layerwise_inference if isinstance(model, models.GAT) else layerwise_inference
+    gatv2_layerwise_inference for models.GATv2, layerwise_inference for everything else (which refuses what it cannot
+    do, models.PinSAGE, with a reason)"""
+    fn = (gat_layerwise_inference if isinstance(model, models.GAT) else
+          gatv2_layerwise_inference if isinstance(model, models.GATv2) else layerwise_inference)
     return fn(model, indptr, indices, feat, batch_rows=batch_rows, device=device)

@@ -113,6 +113,10 @@ SIGNATURES = {
     "fgnn_csr_gat_max_heads": (_Z, ()),
     "fgnn_csr_gat_workspace_bytes": (_Z, (_Z, _Z, _Z, _Z)),
     "fgnn_csr_gat_attention": (_I, (_P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _Z, _Z, _Z, _F, _P, _Z, _P, _Z, _P)),
+    "fgnn_csr_gatv2_max_feats": (_Z, ()),
+    "fgnn_csr_gatv2_block_edges": (_Z, ()),
+    "fgnn_csr_gatv2_workspace_bytes": (_Z, (_Z, _Z, _Z, _Z)),
+    "fgnn_csr_gatv2_attention": (_I, (_P, _P, _P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, _Z, _F, _P, _Z, _P, _Z, _P)),
     "fgnn_relu_l2norm": (_I, (_P, _Z, _P, _Z, _P, _Z, _Z, _P)),
     "fgnn_relu_l2norm_backward": (_I, (_P, _Z, _P, _P, _Z, _P, _Z, _Z, _Z, _P)),
     "fgnn_gat_workspace_bytes": (_Z, (_Z, _Z, _Z)),

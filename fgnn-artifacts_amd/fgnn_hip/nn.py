@@ -535,6 +535,62 @@ def csr_gat_attention_into(out, feat, el, er, indptr, indices, nodes=None, first
     return out
 
 
+# ---- GATv2 attention over whole CSR rows: exact layer-wise GATv2 inference (csrc/csr_gatv2_attention.hip) --------------
+
+def csr_gatv2_max_feats():
+    """features per head the kernel serves (fgnn_csr_gatv2_max_feats: a head must fit the columns a wave holds at a
+    time); more are refused.  Any number of heads."""
+    return int(_lib.load().fgnn_csr_gatv2_max_feats())
+
+
+def csr_gatv2_block_edges():
+    """B: edges of a block of the kernel's online softmax (fgnn_csr_gatv2_block_edges)"""
+    return int(_lib.load().fgnn_csr_gatv2_block_edges())
+
+
+def csr_gatv2_workspace(device, num_rows, max_edges, H, F):
+    """the scratch of fgnn_csr_gatv2_attention for these sizes on `device` (hub queue, piece descriptors, partial rows),
+    cached per (device, bytes) together with csr_workspace's; the call expects nothing of its contents.  Calls that run
+    concurrently on different streams need workspaces of their own."""
+    nbytes = _lib.load().fgnn_csr_gatv2_workspace_bytes(num_rows, max_edges, H, F)
+    return _csr_ws(device, nbytes), nbytes
+
+
+def csr_gatv2_attention_into(out, fs, fd, attn, indptr, indices, nodes=None, first=0, count=None, negative_slope=0.2,
+                             max_edges=None):
+    """out[i, h, :] = sum over v's CSR row of a[p, h] * fs[indices[p], h, :] with a[., h] = softmax over the row of
+    sum_f attn[h, f] * leaky_relu(fs[indices[p], h, f] + fd[v, h, f], negative_slope), for v = nodes[i], or v = first + i
+    for i < count (default: out's rows): fgnn_csr_gatv2_attention, no autograd, no dropout.  out [rows, H, F] (fp32) is
+    OVERWRITTEN -- no zero fill, rows without a neighbour become zeros --, fs and fd are [N, H, F] fp32, one row per
+    NODE (fd too, unlike gatv2_forward_into's; it may be fs itself: share_weights); all three may be column blocks of
+    wider row-major matrices.  attn holds H F contiguous values.  indptr / indices: the int32-viewed u32 CSR tensors the
+    engine uses.  Every fs row is read once; no float atomics: a row's bits depend on the row alone, whatever else the
+    call computes.  F <= csr_gatv2_max_feats().  max_edges: upper bound of the summed lengths of the call's rows
+    (default: the graph's edge count, which holds unless `nodes` repeats ids; rows beyond the bound are still right,
+    only computed by one wave each)."""
+    assert _rows_ok(out) and _rows_ok(fs) and _rows_ok(fd) and fs.shape[1:] == out.shape[1:] and fd.shape == fs.shape
+    N, H, F = fs.shape
+    assert attn.dtype == torch.float32 and attn.is_contiguous() and attn.numel() == H * F
+    assert F <= csr_gatv2_max_feats()
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    if nodes is not None:
+        assert nodes.dtype == torch.int32 and nodes.is_contiguous() and count is None
+        count = nodes.numel()
+    elif count is None:
+        count = out.shape[0]
+    assert out.shape[0] >= count and (nodes is not None or first + count <= indptr.numel() - 1)
+    _lib._need_gpu(out, fs, fd, attn, indptr, indices, nodes)
+    if max_edges is None:
+        max_edges = indices.numel()
+    ws, nbytes = csr_gatv2_workspace(fs.device, count, max_edges, H, F)
+    code = _lib.load().fgnn_csr_gatv2_attention(_ptr(indptr), _ptr(indices), _ptr(nodes), first, count, max_edges,
+                                                _ptr(fs), fs.stride(0), _ptr(fd), fd.stride(0), _ptr(attn), H, F,
+                                                negative_slope, _ptr(out), out.stride(0), _ptr(ws), nbytes, _st(fs))
+    _lib._check(code, "fgnn_csr_gatv2_attention")
+    return out
+
+
 class _XentWs:
     """scratch of fgnn_softmax_xent per (device, n): arrival counter (zeroed once) + row losses"""
     cache = {}

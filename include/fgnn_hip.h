@@ -480,6 +480,36 @@ int fgnn_csr_gat_attention(const uint32_t *indptr, const uint32_t *indices, cons
                            size_t feat_ld, size_t num_head, size_t num_feat, float negative_slope, float *out,
                            size_t out_ld, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- GATv2 attention over whole CSR rows (csrc/csr_gatv2_attention.hip; exact layer-wise GATv2 inference:
+ * examples/inference.py gatv2_layerwise_inference) -------------------------------------------------------------------------
+ * num_head heads H of num_feat features F.  For output row i < num_rows, with v = nodes ? nodes[i] : first + i and the
+ * CSR range [indptr[v], indptr[v + 1]):
+ *   s[p, h] = sum over f of attn[h * F + f] * leaky_relu(fs[indices[p] * fs_ld + h * F + f] + fd[v * fd_ld + h * F + f],
+ *                                                        negative_slope)
+ *   a[p, h] = softmax of s[., h] over the row
+ *   out[i * out_ld + h * F + f] = sum over p of a[p, h] * fs[indices[p] * fs_ld + h * F + f]
+ * fs and fd are fp32 rows with a stride, one per NODE (fd too; fd may be fs), attn holds H F contiguous floats.  out is
+ * OVERWRITTEN; a row without a neighbour becomes zeros.  Inference only: no dropout, no alpha output, no gradient; the
+ * residual and the activation are the caller's.  As fgnn_csr_gat_attention: one wave owns an output row, no float
+ * atomics, rows of more than fgnn_csr_split_length() edges are cut into pieces that other waves compute into `ws` and
+ * that are combined in piece order.  Every fs element is read ONCE: a piece is walked in CSR order in blocks of
+ * fgnn_csr_gatv2_block_edges() edges with an online softmax (per block: m' = max(m, s_j), c = exp(m - m'), acc = c acc +
+ * exp(s_j - m') fs_j .., z = c z + exp(s_j - m') .., from m = -inf, acc = z = 0; row: m = max m_k, c_k = exp(m_k - m),
+ * out = sum c_k acc_k / sum c_k z_k), so a node's result is bit for bit the same whatever else a call computes;
+ * everything is enqueued on `stream` without a host synchronisation.  max_edges and ws as for fgnn_csr_aggregate,
+ * ws_bytes >= fgnn_csr_gatv2_workspace_bytes(num_rows, max_edges, num_head, num_feat).  num_rows == 0 returns FGNN_OK and
+ * touches nothing.  FGNN_EINVAL before any launch: a null required pointer, a pointer that is not 4-byte aligned,
+ * num_head or num_feat 0, num_feat > fgnn_csr_gatv2_max_feats() (a head must fit the 256 columns a wave holds at a
+ * time; any num_head), a stride below H F, first + num_rows or max_edges beyond 2^32, a workspace that is too small or
+ * not 16-byte aligned. */
+size_t fgnn_csr_gatv2_max_feats(void);
+size_t fgnn_csr_gatv2_block_edges(void);
+size_t fgnn_csr_gatv2_workspace_bytes(size_t num_rows, size_t max_edges, size_t num_head, size_t num_feat);
+int fgnn_csr_gatv2_attention(const uint32_t *indptr, const uint32_t *indices, const uint32_t *nodes, size_t first,
+                             size_t num_rows, size_t max_edges, const float *fs, size_t fs_ld, const float *fd,
+                             size_t fd_ld, const float *attn, size_t num_head, size_t num_feat, float negative_slope,
+                             float *out, size_t out_ld, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- fused GAT layer: edge-softmax attention and its aggregation (csrc/gat_attention.hip; examples/models.py
  * FusedGATConv; reference: dgl.nn.GATConv of example/samgraph/train_gat.py) ------------------------------------------------
  * num_head heads H of num_feat features F each; feat / out / gout / gfeat are [rows, H, F] with a row stride (>= H F

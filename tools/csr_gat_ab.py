@@ -7,8 +7,11 @@ graph's average degree, for 8 heads of 32 and of 64 features.  Interleaved alter
 and spread of --ab rounds of --steps launches each; bytes counted as E x (feat row + el row + index) read and rows x H F
 x 4 written -- what the CSR kernel needs, not what the baseline moves on top.  The outputs of the two are compared
 first.  No ratio is fixed in advance: the verdict is printed as it comes out.
-usage: csr_gat_ab.py [--num-node 4000000] [--num-edge 58000000] [--shapes 8x32 8x64] [--ab 7] [--steps 10]
-                     [--out profiles/r12_a_csr_gat_ab.txt]"""
+--model gatv2: the same comparison for fgnn_csr_gatv2_attention (one pass, online softmax in fixed blocks) against
+fgnn_gatv2_forward plus its zero fill; bytes = E x (fs row + index) read once + rows x (fd row read + out row written);
+default output profiles/r14_a_csr_gatv2_ab.txt.
+usage: csr_gat_ab.py [--model gat|gatv2] [--num-node 4000000] [--num-edge 58000000] [--shapes 8x32 8x64] [--ab 7]
+                     [--steps 10] [--out profiles/r12_a_csr_gat_ab.txt]"""
 import argparse
 import os
 import statistics
@@ -26,8 +29,12 @@ ap.add_argument("--num-edge", type=int, default=58_000_000, help="default: paper
 ap.add_argument("--shapes", nargs="+", default=["8x32", "8x64"], help="heads x features")
 ap.add_argument("--ab", type=int, default=7)
 ap.add_argument("--steps", type=int, default=10)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_a_csr_gat_ab.txt"))
+ap.add_argument("--model", choices=["gat", "gatv2"], default="gat")
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+v2 = args.model == "gatv2"
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "r14_a_csr_gatv2_ab.txt" if v2 else "r12_a_csr_gat_ab.txt")
 lib.load()
 dev = torch.device("cuda:0")
 lines = []
@@ -50,20 +57,31 @@ for shape in args.shapes:
     H, F = (int(v) for v in shape.split("x"))
     feat = torch.empty((N, H, F), dtype=torch.float32, device=dev).normal_()
     el, er = (torch.empty((N, H), dtype=torch.float32, device=dev).normal_() for _ in range(2))
+    if v2:  # feat is fs; scores of a few units, as el + er gives
+        fd = torch.empty((N, H, F), dtype=torch.float32, device=dev).normal_()
+        attn = torch.empty((H, F), dtype=torch.float32, device=dev).normal_() / F ** 0.5
     outs = {"csr": torch.empty((N, H, F), dtype=torch.float32, device=dev),
             "coo": torch.empty((N, H, F), dtype=torch.float32, device=dev)}
     alpha = torch.empty((E, H), dtype=torch.float32, device=dev)
     say("%s: the COO baseline writes and reads %.0f MB of alphas, %.0f MB of scratch and reads %.0f MB of destination "
         "ids on top; the CSR kernel's workspace is %.1f MB"
-        % (shape, 4 * E * H / 1e6, lib.load().fgnn_gat_workspace_bytes(E, N, H) / 1e6, 4 * E / 1e6,
-           lib.load().fgnn_csr_gat_workspace_bytes(N, E, H, F) / 1e6))
+        % (shape, 4 * E * H / 1e6,
+           (lib.load().fgnn_gatv2_workspace_bytes if v2 else lib.load().fgnn_gat_workspace_bytes)(E, N, H) / 1e6,
+           4 * E / 1e6,
+           (lib.load().fgnn_csr_gatv2_workspace_bytes if v2 else lib.load().fgnn_csr_gat_workspace_bytes)(N, E, H, F)
+           / 1e6))
 
     def launch(name):
-        if name == "csr":
+        if name == "csr" and v2:
+            nn.csr_gatv2_attention_into(outs["csr"], feat, fd, attn, indptr, indices)
+        elif name == "csr":
             nn.csr_gat_attention_into(outs["csr"], feat, el, er, indptr, indices)
         else:
             outs["coo"].zero_()
-            nn.gat_forward_into(outs["coo"], alpha, feat, el, er, indices, col)
+            if v2:
+                nn.gatv2_forward_into(outs["coo"], alpha, feat, fd, attn, indices, col)
+            else:
+                nn.gat_forward_into(outs["coo"], alpha, feat, el, er, indices, col)
 
     def run(name, n):
         e0.record()
@@ -82,7 +100,7 @@ for shape in args.shapes:
     for _ in range(args.ab):
         for name in outs:
             us[name].append(run(name, args.steps))
-    gb = (E * (H * F * 4 + H * 4 + 4) + N * H * F * 4) / 1e9
+    gb = (E * (H * F * 4 + 4) + 2 * N * H * F * 4 if v2 else E * (H * F * 4 + H * 4 + 4) + N * H * F * 4) / 1e9
     for name, v in us.items():
         med = statistics.median(v)
         say("%s %s: median %.0f us per call, min %.0f, max %.0f, spread %.0f; %.2f GB read + written = %.0f GB/s  (%s)"
@@ -95,5 +113,7 @@ for shape in args.shapes:
     say("%s: csr median / coo median = %.2f (csr - coo = %.0f us, the larger spread of the two %.0f us): %s"
         % (shape, med["csr"] / med["coo"], diff, spread, verdict))
     del feat, el, er, outs, alpha
+    if v2:
+        del fd, attn
 with open(args.out, "w") as f:
     f.write("\n".join(lines) + "\n")
