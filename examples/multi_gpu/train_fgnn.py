@@ -99,7 +99,7 @@ def get_run_config(args):
         st = args.sample_type or ("khop2" if args.model == "graphsage" else "khop0")
         fan = args.fanout or ([25, 10] if args.model == "graphsage" else [5, 10, 15])
         rc.update(num_fanout=len(fan), fanout=fan, num_layer=len(fan))
-    rc["_sample_type"] = sam.sample_types[st]
+    rc["_sample_type"] = sam.all_sample_types[st]
     if args.feat_store != "f32":  # (the key is optional: without it the engine's run is the fp32 one, byte for byte)
         rc["feat_store_dtype"] = args.feat_store
     n_dev = torch.cuda.device_count()

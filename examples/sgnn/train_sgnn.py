@@ -67,7 +67,7 @@ def get_run_config(args):
         st = args.sample_type or ("khop2" if args.model == "graphsage" else "khop0")
         fan = args.fanout or ([25, 10] if args.model == "graphsage" else [5, 10, 15])
         rc.update(num_fanout=len(fan), fanout=fan, num_layer=len(fan))
-    rc["_sample_type"] = sam.sample_types[st]
+    rc["_sample_type"] = sam.all_sample_types[st]
     shared = args.single_gpu or torch.cuda.device_count() < nw
     rc["workers"] = ["cuda:0"] * nw if shared else ["cuda:%d" % i for i in range(nw)]
     # RCCL refuses two ranks on one device: the one-GPU layout synchronises gradients over gloo

@@ -101,7 +101,7 @@ def main():
     if arch == "arch4" and two:
         trainer_ctx = "cuda:0"  # builtin_archs['arch4'] (samgraph/common/__init__.py:118-122)
     run_config = dict(dataset_path=args.dataset_path, _arch=sam.builtin_archs[arch]["arch"],
-                      _sample_type=sam.sample_types[args.sample_type],
+                      _sample_type=sam.all_sample_types[args.sample_type],
                       batch_size=args.batch_size, num_epoch=args.num_epoch + 1,  # + one warm-up epoch (common_config.py:163)
                       _cache_policy=sam.cache_policies[args.cache_policy], cache_percentage=args.cache_percentage, max_sampling_jobs=10,
                       max_copying_jobs=2, omp_thread_num=8, sampler_ctx=sampler_ctx, trainer_ctx=trainer_ctx)

@@ -173,6 +173,13 @@ extern "C" fgnn_sampler *fgnn_sampler_create(const fgnn_sampler_config *cfg, int
     case FGNN_RANDOM_WALK:
       if (cfg->walk_len == 0 || cfg->num_walks == 0) return fail(FGNN_EINVAL);
       break;
+    case FGNN_KHOP_SHARED: {
+      uint32_t params[3];
+      fgnn_khop_shared_params(params);
+      for (size_t l = 0; l < cfg->num_layers; ++l)
+        if (cfg->fanout[l] > params[0]) return fail(FGNN_EINVAL);
+      break;
+    }
     default:
       return fail(FGNN_EINVAL);
   }
@@ -200,6 +207,7 @@ extern "C" fgnn_sampler *fgnn_sampler_create(const fgnn_sampler_config *cfg, int
     size_t need = 0;
     if (uses_rank_bitmap(cfg->sample_type)) need = fgnn_weighted_scratch_bytes(s->in_cap[l], cfg->fanout[l]);
     if (cfg->sample_type == FGNN_RANDOM_WALK) need = fgnn_random_walk_scratch_bytes(s->in_cap[l], cfg->fanout[l]);
+    if (cfg->sample_type == FGNN_KHOP_SHARED) need = fgnn_khop_shared_scratch_bytes(s->in_cap[l], cfg->fanout[l]);
     if (need > s->ws_bytes) s->ws_bytes = need;
   }
   for (auto &sl : s->slot) {
@@ -533,6 +541,9 @@ int sample_chain(fgnn_sampler *s, uint64_t seq, const uint32_t *d_seeds, size_t 
       }
       case FGNN_WEIGHTED_KHOP_HASH_DEDUP:
         rc = fgnn::sample_hash_dedup(call, s->cfg.prob_table, s->cfg.alias_table, &sl.scan_sample);
+        break;
+      case FGNN_KHOP_SHARED:
+        rc = fgnn::sample_khop_shared(call, &sl.scan_sample);
         break;
       case FGNN_RANDOM_WALK:
         // fanout[l] == RunConfig::num_neighbor (CHECK_EQ at cuda_loops.cc:129)

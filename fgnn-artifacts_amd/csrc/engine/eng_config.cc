@@ -2,6 +2,8 @@
 
 #include <cstring>
 
+#include "fgnn_hip.h"
+
 namespace sam {
 
 int MinLogLevel() {
@@ -127,6 +129,12 @@ void RunConfig::Parse(const char **keys, const char **vals, size_t n) {
       // larger fanout its sampler never returns
       for (size_t f : fanout) SAM_CHECK(f <= 50) << "weighted_khop_hash_dedup: fanout " << f << " > 50";
       break;
+    case kKHopShared: {  // not a reference sample type (sample_khop_shared.hip); the kernel library names its limit
+      uint32_t params[3];
+      fgnn_khop_shared_params(params);
+      for (size_t f : fanout) SAM_CHECK(f <= params[0]) << "khop_shared: fanout " << f << " > " << params[0];
+      break;
+    }
     default: SAM_FATAL << "unknown sample type " << sample_type;
   }
   is_configured = true;

@@ -9,7 +9,8 @@
 namespace sam {
 
 enum RunArch { kArch0 = 0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 };
-enum SampleType { kKHop0 = 0, kKHop1, kWeightedKHop, kRandomWalk, kWeightedKHopPrefix, kKHop2, kWeightedKHopHashDedup };
+enum SampleType { kKHop0 = 0, kKHop1, kWeightedKHop, kRandomWalk, kWeightedKHopPrefix, kKHop2, kWeightedKHopHashDedup,
+                  kKHopShared = 8 /* this engine's own: one random key per node, shared by a layer's seeds; 7 stays unknown */ };
 enum CachePolicy {
   kCacheByDegree = 0, kCacheByHeuristic, kCacheByPreSample, kCacheByDegreeHop, kCacheByPreSampleStatic,
   kCacheByFakeOptimal, kDynamicCache, kCacheByRandom

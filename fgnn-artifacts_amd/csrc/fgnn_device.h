@@ -891,6 +891,9 @@ int sample_with_replacement(const LayerCall &c, int sample_type, const float *ta
                             PrefixTreeView tree = PrefixTreeView{nullptr, nullptr, nullptr});
 // fgnn_sample_weighted_khop_hash_dedup; scan: the slot's look-back descriptors (null: descriptors in ws)
 int sample_hash_dedup(const LayerCall &c, const float *prob_table, const uint32_t *alias_table, ScanWsHost *scan);
+// fgnn_sample_khop_shared (sample_khop_shared.hip): one key per node, shared by the seeds of a layer.  scan: the slot's
+// look-back descriptors -- offsets and output from one launch (null, or too many tiles: count -> scan -> emit)
+int sample_khop_shared(const LayerCall &c, ScanWsHost *scan);
 // fgnn_sample_random_walk (K = c.fanout); scan: look-back descriptors -- the edge offsets and the compacted output then
 // come from one launch (null: per-workgroup sums -> scan -> emit)
 int sample_random_walk(const LayerCall &c, size_t walk_len, double restart_prob, size_t num_walks, uint32_t *out_data,

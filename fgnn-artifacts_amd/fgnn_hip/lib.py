@@ -74,6 +74,9 @@ SIGNATURES = {
     "fgnn_hash_dedup_scratch_bytes": (_Z, (_Z,)),
     "fgnn_sample_weighted_khop_hash_dedup": (_I, (_P, _P, _P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32,
                                                 _P, _Z, _P)),
+    "fgnn_khop_shared_scratch_bytes": (_Z, (_Z, _Z)),
+    "fgnn_khop_shared_params": (None, (_P,)),
+    "fgnn_sample_khop_shared": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32, _P, _Z, _P)),
     "fgnn_random_walk_scratch_bytes": (_Z, (_Z, _Z)),
     "fgnn_sample_random_walk": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _D, _Z, _Z, _P, _P, _P, _P, _I, _U64, _U64, _U32, _P,
                                    _Z, _P)),
@@ -392,6 +395,31 @@ def sample_with_replacement(kind, indptr, indices, inp, fanout, seed, batch_key,
     return out_src, out_dst, d_num_out
 
 
+def khop_shared_params():
+    """fgnn_khop_shared_params: largest fanout, longest row a wave selects alone, longest row a workgroup selects alone
+    (longer rows are first reduced by all workgroups).  Needs no GPU."""
+    out = (C.c_uint32 * 3)()
+    load().fgnn_khop_shared_params(out)
+    return dict(zip(("max_fanout", "wave_row", "block_row"), (int(v) for v in out)))
+
+
+def sample_khop_shared(indptr, indices, inp, fanout, seed, batch_key, layer, src_mode=SRC_GLOBAL, d_num_input=None,
+                       ws=None):
+    """Shared-key sampling (fgnn_sample_khop_shared): returns (out_src, out_dst, d_num_out) like sample_khop."""
+    L = load()
+    _need_gpu(indptr, indices, inp)
+    n, dev = inp.numel(), inp.device
+    out_src = torch.empty(max(n * fanout, 1), dtype=torch.int32, device=dev)
+    out_dst = torch.empty(max(n * fanout, 1), dtype=torch.int32, device=dev)
+    d_num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    if ws is None:
+        ws = torch.empty(L.fgnn_khop_shared_scratch_bytes(max(n, 1), fanout), dtype=torch.uint8, device=dev)
+    _check(L.fgnn_sample_khop_shared(_ptr(indptr), _ptr(indices), _ptr(inp), n, _ptr(d_num_input), n, fanout,
+                                     _ptr(out_src), _ptr(out_dst), _ptr(d_num_out), src_mode, seed, batch_key, layer,
+                                     _ptr(ws), ws.numel(), _stream()), "fgnn_sample_khop_shared")
+    return out_src, out_dst, d_num_out
+
+
 def sample_random_walk(indptr, indices, inp, walk_len, restart_prob, num_walks, K, seed, batch_key, layer,
                        src_mode=SRC_GLOBAL, d_num_input=None):
     L = load()
@@ -688,6 +716,7 @@ def extract_fused(out, miss_rows, cache_rows, miss_src, miss_dst, cache_src, cac
 
 MAX_LAYERS = 8
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP = 0, 1, 2, 3, 4, 5, 6
+KHOP_SHARED = 8  # (7 stays an unknown type) not a sample type of the reference: one random key per node, shared by a layer's seeds
 
 
 class SamplerConfig(C.Structure):

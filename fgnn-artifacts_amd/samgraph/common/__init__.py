@@ -31,6 +31,7 @@ def _enum(names, start=0):
 # DeviceType, SampleType, RunArch, CachePolicy -- common.h:38-92
 _enum(["kCPU", "kMMAP", "kGPU"])
 _enum(["kKHop0", "kKHop1", "kWeightedKHop", "kRandomWalk", "kWeightedKHopPrefix", "kKHop2", "kWeightedKHopHashDedup"])
+kKHopShared = 8  # this engine's own (see ext_sample_types); 7, the first value the reference refuses, stays refused
 _enum(["kArch%d" % i for i in range(8)])
 _enum(["kCacheByDegree", "kCacheByHeuristic", "kCacheByPreSample", "kCacheByDegreeHop", "kCacheByPreSampleStatic",
        "kCacheByFakeOptimal", "kDynamicCache", "kCacheByRandom"])
@@ -53,6 +54,13 @@ sample_types = {
     "weighted_khop": kWeightedKHop, "weighted_khop_prefix": kWeightedKHopPrefix,  # noqa: F821
     "weighted_khop_hash_dedup": kWeightedKHopHashDedup,  # noqa: F821
 }
+
+# Sample types the reference does not have.  `sample_types` stays the reference's dict, entry for entry (it is pinned
+# against the reference's module); scripts that want to offer these as well look names up in `all_sample_types`.
+# khop_shared: one random key per node and batch, shared by all seeds of a layer -- each seed still draws a uniform
+# fanout-subset of its row, but seeds with common neighbours pick the same ones (csrc/sample_khop_shared.hip)
+ext_sample_types = {"khop_shared": kKHopShared}
+all_sample_types = dict(sample_types, **ext_sample_types)
 
 builtin_archs = {
     "arch0": {"arch": kArch0, "sampler_ctx": cpu(), "trainer_ctx": gpu(0)},  # noqa: F821

@@ -34,9 +34,9 @@ extern "C" {
 
 /* DataType, common.h:38-46 */
 enum { FGNN_F32 = 0, FGNN_F64 = 1, FGNN_F16 = 2, FGNN_U8 = 3, FGNN_I32 = 4, FGNN_I8 = 5, FGNN_I64 = 6 };
-/* SampleType, common.h:50-58 (only used to derive RNG tags) */
+/* SampleType, common.h:50-58 (only used to derive RNG tags); FGNN_KHOP_SHARED is this library's own */
 enum { FGNN_KHOP0 = 0, FGNN_KHOP1 = 1, FGNN_WEIGHTED_KHOP = 2, FGNN_RANDOM_WALK = 3, FGNN_WEIGHTED_KHOP_PREFIX = 4,
-       FGNN_KHOP2 = 5, FGNN_WEIGHTED_KHOP_HASH_DEDUP = 6 };
+       FGNN_KHOP2 = 5, FGNN_WEIGHTED_KHOP_HASH_DEDUP = 6, FGNN_KHOP_SHARED = 8 /* 7 stays unknown */ };
 
 /* out_src contents of the samplers */
 enum { FGNN_SRC_GLOBAL = 0, /* seed's global id, as the reference emits (khop2.cu:79) */
@@ -198,6 +198,20 @@ int fgnn_sample_weighted_khop_hash_dedup(const uint32_t *indptr, const uint32_t 
                                          uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out, int src_mode,
                                          uint64_t seed, uint64_t batch_key, uint32_t layer, void *ws, size_t ws_bytes,
                                          void *stream);
+
+/* Shared-key neighbour sampling (no reference twin; the fixed-fanout form of LABOR, Balin & Catalyurek): every node t
+ * has one random word per (seed, batch_key, layer), w(t) = word t & 3 of the Philox block (item t >> 2, block 0) under
+ * the tag of FGNN_KHOP_SHARED; a seed keeps the `fanout` positions j of its row with the smallest (w(t_j) << 32) | j
+ * (rows of <= fanout entries whole), in CSR order, compacted COO like khop0.  Each seed's sample is a uniform
+ * fanout-subset; seeds with overlapping rows pick the same neighbours.  indices is not modified.  fanout <= out[0] of
+ * fgnn_khop_shared_params, whose out[1], out[2] are the row lengths up to which a wave / a workgroup selects a row
+ * alone (longer rows are first reduced by all workgroups).  Scratch (8-byte aligned): fgnn_khop_shared_scratch_bytes. */
+size_t fgnn_khop_shared_scratch_bytes(size_t num_input_cap, size_t fanout);
+void fgnn_khop_shared_params(uint32_t out[3]);
+int fgnn_sample_khop_shared(const uint32_t *indptr, const uint32_t *indices, const uint32_t *input, size_t num_input,
+                            const uint32_t *d_num_input, size_t num_input_cap, size_t fanout, uint32_t *out_src,
+                            uint32_t *out_dst, size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key,
+                            uint32_t layer, void *ws, size_t ws_bytes, void *stream);
 
 /* GPUSampleRandomWalk + FrequencyHashmap::GetTopK (cuda_sampling_random_walk.cu:113-161,
  * cuda_frequency_hashmap.cu:1143-1367): num_walks restart walks of walk_len steps per seed; per seed

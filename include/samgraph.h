@@ -19,7 +19,8 @@
  * worker process, each worker samples and extracts its equal share of the train set, dist/dist_loops_arch6.cc,
  * dist/dist_shuffler_aligned.cc) and arch7 (a sample-only engine per worker: samgraph_config with worker_id /
  * num_worker + samgraph_init in every worker, cuda/cuda_loops_arch7.cc).  Sample types: all seven (khop0,
- * khop1, khop2, weighted_khop, weighted_khop_hash_dedup, weighted_khop_prefix, random_walk).  Cache policies: every
+ * khop1, khop2, weighted_khop, weighted_khop_hash_dedup, weighted_khop_prefix, random_walk) and one of this engine's
+ * own, khop_shared (_sample_type 8: one random key per node, shared by a layer's seeds; fgnn_hip.h).  Cache policies: every
  * _cache_policy value of the reference -- pre_sample (computed at sample_init, dist/pre_sampler.cc), presample_static
  * (whole-neighbourhood frequencies, cuda/pre_sampler.cc:69-71; refused by the multi-process engine like
  * dist/pre_sampler.cc:87-88), dynamic_cache (arch4) and the file-backed rankings (cache_by_*.bin, engine.cc:216-256).
