@@ -496,6 +496,23 @@ extern "C" void fgnn_khop_shared_params(uint32_t out[3]) {
   out[2] = fgnn::kBlockRow;
 }
 
+extern "C" void fgnn_khop_shared_pool_params(uint32_t out[2]) {
+  out[0] = fgnn::kMaxHubs;
+  out[1] = fgnn::kHubPool;
+}
+
+extern "C" int fgnn_debug_khop_shared_hub_state(const void *ws, size_t num_input_cap, unsigned long long out[3]) {
+  if (!ws || !num_input_cap || !out || (reinterpret_cast<uintptr_t>(ws) & 7u)) return FGNN_EINVAL;
+  FGNN_HIP_CHECK(hipDeviceSynchronize());
+  uint32_t header[4];  // count, end, used (64 bits)
+  FGNN_HIP_CHECK(hipMemcpy(header, static_cast<const uint32_t *>(ws) + fgnn::ws_layout(num_input_cap).header,
+                           sizeof(header), hipMemcpyDeviceToHost));
+  out[0] = header[0];
+  out[1] = header[1];
+  out[2] = (unsigned long long)header[3] << 32 | header[2];
+  return FGNN_OK;
+}
+
 extern "C" int fgnn_sample_khop_shared(const uint32_t *indptr, const uint32_t *indices, const uint32_t *input,
                                        size_t num_input, const uint32_t *d_num_input, size_t num_input_cap,
                                        size_t fanout, uint32_t *out_src, uint32_t *out_dst, size_t *d_num_out,

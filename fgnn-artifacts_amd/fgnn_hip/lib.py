@@ -76,6 +76,8 @@ SIGNATURES = {
                                                 _P, _Z, _P)),
     "fgnn_khop_shared_scratch_bytes": (_Z, (_Z, _Z)),
     "fgnn_khop_shared_params": (None, (_P,)),
+    "fgnn_khop_shared_pool_params": (None, (_P,)),
+    "fgnn_debug_khop_shared_hub_state": (_I, (_P, _Z, _P)),
     "fgnn_sample_khop_shared": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _P, _P, _I, _U64, _U64, _U32, _P, _Z, _P)),
     "fgnn_random_walk_scratch_bytes": (_Z, (_Z, _Z)),
     "fgnn_sample_random_walk": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _D, _Z, _Z, _P, _P, _P, _P, _I, _U64, _U64, _U32, _P,
@@ -401,6 +403,22 @@ def khop_shared_params():
     out = (C.c_uint32 * 3)()
     load().fgnn_khop_shared_params(out)
     return dict(zip(("max_fanout", "wave_row", "block_row"), (int(v) for v in out)))
+
+
+def khop_shared_pool_params():
+    """fgnn_khop_shared_pool_params: rows the hub list holds, pairs the candidate pool holds.  Needs no GPU."""
+    out = (C.c_uint32 * 2)()
+    load().fgnn_khop_shared_pool_params(out)
+    return dict(zip(("max_hubs", "hub_pool"), (int(v) for v in out)))
+
+
+def debug_khop_shared_hub_state(ws, num_input_cap):
+    """fgnn_debug_khop_shared_hub_state: (hubs counted, end of the last pool claim with room, pairs claimed) of the last
+    sample_khop_shared call that was given the scratch tensor `ws`.  Synchronises."""
+    _need_gpu(ws)
+    out = (C.c_ulonglong * 3)()
+    _check(load().fgnn_debug_khop_shared_hub_state(_ptr(ws), num_input_cap, out), "fgnn_debug_khop_shared_hub_state")
+    return dict(zip(("count", "end", "used"), (int(v) for v in out)))
 
 
 def sample_khop_shared(indptr, indices, inp, fanout, seed, batch_key, layer, src_mode=SRC_GLOBAL, d_num_input=None,

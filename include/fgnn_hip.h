@@ -208,6 +208,13 @@ int fgnn_sample_weighted_khop_hash_dedup(const uint32_t *indptr, const uint32_t 
  * alone (longer rows are first reduced by all workgroups).  Scratch (8-byte aligned): fgnn_khop_shared_scratch_bytes. */
 size_t fgnn_khop_shared_scratch_bytes(size_t num_input_cap, size_t fanout);
 void fgnn_khop_shared_params(uint32_t out[3]);
+/* Sizes of the hub workspace: out[0] rows the hub list holds, out[1] (word, position) pairs the candidate pool holds.
+ * A hub beyond either is selected by its owner from the row itself. */
+void fgnn_khop_shared_pool_params(uint32_t out[2]);
+/* Diagnostics (tests): what the hub scan of the last fgnn_sample_khop_shared call on the scratch buffer `ws` (same
+ * num_input_cap) left behind: out[0] hubs counted (beyond the list's size: the surplus was not listed), out[1] end of
+ * the last pool claim that found room, out[2] pairs claimed with or without room.  Synchronises the device. */
+int fgnn_debug_khop_shared_hub_state(const void *ws, size_t num_input_cap, unsigned long long out[3]);
 int fgnn_sample_khop_shared(const uint32_t *indptr, const uint32_t *indices, const uint32_t *input, size_t num_input,
                             const uint32_t *d_num_input, size_t num_input_cap, size_t fanout, uint32_t *out_src,
                             uint32_t *out_dst, size_t *d_num_out, int src_mode, uint64_t seed, uint64_t batch_key,

@@ -56,6 +56,9 @@ def test_signature_table_equals_the_header():
     for name, sig in protos.items():
         assert lib.SIGNATURES[name] == sig, name
     assert lib.EXPORTS == list(lib.SIGNATURES)
+    # read-only entry points of the shared-key sampler: sizes into an array; a scratch buffer's hub counters
+    assert protos["fgnn_khop_shared_pool_params"] == (None, (C.c_void_p,))
+    assert protos["fgnn_debug_khop_shared_hub_state"] == (C.c_int, (C.c_void_p, C.c_size_t, C.c_void_p))
 
 
 def test_every_function_of_the_loaded_library_is_typed():

@@ -118,6 +118,43 @@ def test_gather_debug_entry_point_is_declared_exported_bound_and_documented(hip_
     assert fn(0xFFFFFC00, 16, 1, 1, 0xFFFFFFFF, 256, 4, 4, out, 2) == -1
 
 
+KHOP_SHARED_ENTRY_POINTS = ["fgnn_sample_khop_shared", "fgnn_khop_shared_scratch_bytes", "fgnn_khop_shared_params",
+                            "fgnn_khop_shared_pool_params", "fgnn_debug_khop_shared_hub_state"]
+
+
+def test_khop_shared_entry_points_are_declared_exported_bound_and_documented(hip_lib):
+    """the shared-key sampler's calls and the two read-only ones tests/test_khop_shared_gpu.py shows a pool overflow
+    with: in the header, in the library, in the binding's export list with a signature; the debug reader named where
+    INTEGRATION.md lists the debug entry points; the sizes answer without a GPU and fit each other"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "fgnn-artifacts_amd"))
+    from fgnn_hip import lib
+    declared = _declared("fgnn_hip.h")
+    for name in KHOP_SHARED_ENTRY_POINTS:
+        assert name in declared and hasattr(hip_lib, name) and name in lib.EXPORTS, name
+        assert name in lib.SIGNATURES, name
+    assert "`fgnn_debug_khop_shared_hub_state`" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    assert callable(getattr(lib, "khop_shared_pool_params", None))
+    assert callable(getattr(lib, "debug_khop_shared_hub_state", None))
+    out = (ctypes.c_uint32 * 2)(0xDEADBEEF, 0xDEADBEEF)
+    hip_lib.fgnn_khop_shared_pool_params.restype = None
+    hip_lib.fgnn_khop_shared_pool_params(out)
+    params = (ctypes.c_uint32 * 3)()
+    hip_lib.fgnn_khop_shared_params.restype = None
+    hip_lib.fgnn_khop_shared_params(params)
+    max_hubs, hub_pool = int(out[0]), int(out[1])
+    assert 0 < max_hubs < hub_pool < 2**31 and hub_pool % int(params[0]) == 0
+    # the scratch holds the list (4 words a row), the pool (two words a pair) and the piece map (one word a pair)
+    hip_lib.fgnn_khop_shared_scratch_bytes.restype = ctypes.c_size_t
+    hip_lib.fgnn_khop_shared_scratch_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
+    assert hip_lib.fgnn_khop_shared_scratch_bytes(1, 1) >= 4 * (4 * max_hubs + 3 * hub_pool)
+    # the reader refuses a null or misaligned buffer before it touches the device
+    fn = hip_lib.fgnn_debug_khop_shared_hub_state
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    state = (ctypes.c_ulonglong * 3)()
+    assert fn(None, 8, state) == -1 and fn(4, 8, state) == -1 and fn(8, 0, state) == -1 and fn(8, 8, None) == -1
+
+
 def test_version_and_scratch(hip_lib):
     hip_lib.fgnn_version.restype = ctypes.c_char_p
     assert b"gfx950" in hip_lib.fgnn_version()

@@ -72,8 +72,14 @@ def test_more_hubs_than_the_list_holds_and_more_tiles_than_one_pass():
     rng = np.random.default_rng(3)
     indptr, indices = _graph([rng.integers(0, NUM_NODE, block + 1)], NUM_NODE)
     one_src, one_dst = refs.sample(indptr, indices, [0], 25, SEED, 4, 0)
-    src, dst, d_ne = hip.sample_khop_shared(dev(indptr), dev(indices), dev(np.zeros(16500, np.uint32)), 25, SEED, 4, 0)
+    ws = torch.empty(hip.load().fgnn_khop_shared_scratch_bytes(16500, 25), dtype=torch.uint8, device="cuda")
+    src, dst, d_ne = hip.sample_khop_shared(dev(indptr), dev(indices), dev(np.zeros(16500, np.uint32)), 25, SEED, 4, 0,
+                                            ws=ws)
     assert int(d_ne.cpu()[0]) == 16500 * 25
+    pool = hip.khop_shared_pool_params()
+    state = hip.debug_khop_shared_hub_state(ws, 16500)  # the list was too short, the pool was not
+    assert state["count"] == 16500 > pool["max_hubs"]
+    assert state["used"] == state["end"] == pool["max_hubs"] * 2 * 25 < pool["hub_pool"]
     np.testing.assert_array_equal(u32(dst, 16500 * 25), np.tile(one_dst, 16500))
     np.testing.assert_array_equal(u32(src, 16500 * 25), np.tile(one_src, 16500))
 
@@ -85,6 +91,53 @@ def test_more_hubs_than_the_list_holds_and_more_tiles_than_one_pass():
     assert int(d_ne.cpu()[0]) == n
     np.testing.assert_array_equal(u32(dst, n), indices[seeds])
     np.testing.assert_array_equal(u32(src, n), np.arange(n, dtype=np.uint32))
+
+
+def _hub_rows_as_seeds(rows, seeds, fanout, key):
+    """the stateless entry point over `seeds` (indices into the few distinct `rows`) with a scratch buffer of the test's
+    own; the reference is computed once per distinct row and tiled.  Returns the hub scan's read-back."""
+    indptr, indices = _graph(rows, NUM_NODE)
+    one_src, one_dst = refs.sample(indptr, indices, np.arange(len(rows)), fanout, SEED, key, 0)
+    assert len(one_dst) == len(rows) * fanout
+    ws = torch.empty(hip.load().fgnn_khop_shared_scratch_bytes(len(seeds), fanout), dtype=torch.uint8, device="cuda")
+    src, dst, d_ne = hip.sample_khop_shared(dev(indptr), dev(indices), dev(seeds), fanout, SEED, key, 0, ws=ws)
+    ne = len(seeds) * fanout
+    assert int(d_ne.cpu()[0]) == ne
+    np.testing.assert_array_equal(u32(dst, ne), one_dst.reshape(len(rows), fanout)[seeds].reshape(-1))
+    np.testing.assert_array_equal(u32(src, ne), np.repeat(seeds, fanout))
+    return hip.debug_khop_shared_hub_state(ws, len(seeds))
+
+
+def test_hubs_that_find_no_room_in_the_pool_while_the_list_has_room():
+    """Fewer hubs than the list holds, whose claims together exceed the candidate pool: the hubs that claim first get their
+    pieces reduced by the whole chip, the others (which ones is a race) are streamed by their owners.  The read-back
+    shows that both happened in this run.  Fanout at the limit; rows of 65, 40 and 3 pieces, the last one of five ids
+    only, so that its ties cross the pieces."""
+    p, pool = hip.khop_shared_params(), hip.khop_shared_pool_params()
+    k, block = p["max_fanout"], p["block_row"]
+    rng = np.random.default_rng(31)
+    pieces = np.array([65, 40, 3])
+    rows = [rng.integers(0, NUM_NODE, 64 * block + 100), rng.integers(0, NUM_NODE, 39 * block + 1),
+            rng.choice([5, 6, 7, 8, 9], 2 * block + 100)]
+    assert [(len(r) - 1) // block + 1 for r in rows] == pieces.tolist()
+    seeds = rng.permutation(np.repeat([0, 1, 2], [700, 500, 300])).astype(np.uint32)
+    claims = int((pieces[seeds] * k).sum())
+    assert len(seeds) < pool["max_hubs"] and claims > pool["hub_pool"]
+    state = _hub_rows_as_seeds(rows, seeds, k, 6)
+    assert state["count"] == len(seeds) and state["used"] == claims
+    assert 0 < state["end"] <= pool["hub_pool"]  # some hubs had room; those claiming beyond the end had none
+    assert state["end"] % k == 0 and state["end"] >= pool["hub_pool"] - 65 * k  # the pool filled up to its last claim
+
+
+def test_claims_that_fill_the_pool_and_the_list_exactly():
+    """as many hubs as the list holds, each of four pieces: the last claim ends on the pool's last pair and all have room"""
+    p, pool = hip.khop_shared_params(), hip.khop_shared_pool_params()
+    k, block = p["max_fanout"], p["block_row"]
+    per_hub = pool["hub_pool"] // pool["max_hubs"]
+    assert per_hub * pool["max_hubs"] == pool["hub_pool"] and per_hub % k == 0
+    rows = [np.random.default_rng(32).integers(0, NUM_NODE, (per_hub // k - 1) * block + 5)]
+    state = _hub_rows_as_seeds(rows, np.zeros(pool["max_hubs"], np.uint32), k, 7)
+    assert state == dict(count=pool["max_hubs"], end=pool["hub_pool"], used=pool["hub_pool"])
 
 
 def test_seeds_with_the_same_row_share_their_picks():

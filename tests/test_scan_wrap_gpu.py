@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import khop_shared_refs
 from test_coresidency_gpu import _digest
 from test_hip_parity import SEED, _seeds, dev, host_u32
 
@@ -58,6 +59,8 @@ def _make_sampler(hip, oracle, w, kind, fanouts, max_batch, d_indices):
         hst, ost = dict(khop0=(hip.KHOP0, oracle.KHOP0), khop1=(hip.KHOP1, oracle.KHOP1),
                         khop2=(hip.KHOP2, oracle.KHOP2))[kind]
         return hip.Sampler(d_indptr, d_indices, fanouts, max_batch, sample_type=hst, seed=SEED), ost, {}
+    if kind == "khop_shared":  # no oracle twin: the batches are held to khop_shared_refs.reference_batch
+        return hip.Sampler(d_indptr, d_indices, fanouts, max_batch, sample_type=hip.KHOP_SHARED, seed=SEED), None, {}
     if kind == "weighted_khop_prefix":
         return (hip.Sampler(d_indptr, d_indices, fanouts, max_batch, sample_type=hip.WEIGHTED_KHOP_PREFIX, seed=SEED,
                             prob_prefix=dev(w.prefix)), oracle.WEIGHTED_KHOP_PREFIX, dict(prob_prefix=w.prefix))
@@ -97,13 +100,14 @@ def _assert_wrapped(states, gen_start, what):
             "%s: set %d holds a descriptor of generation %#x, current %#x" % (what, i, st.max_desc_gen, st.gen)
 
 
-def _drive_across_generation_wrap(hip, oracle, w, kind, ticket=-1):
-    """NUM_BATCHES batches of a two-layer sampler through fgnn_sampler_run_batch with a cache table, one batch buffer,
-    every generation set six launches before the limit.  The first three batches have four times the seeds: their
-    grids stamp descriptors that no later, smaller grid writes again."""
+def _drive_across_generation_wrap(hip, oracle, w, kind, ticket=-1, fanouts=None, nseed=300, big=1200,
+                                  num_batches=NUM_BATCHES):
+    """num_batches batches of a two-layer sampler through fgnn_sampler_run_batch with a cache table, one batch buffer,
+    every generation set six launches before the limit.  The first three batches have four times the seeds (`big`): their
+    grids stamp descriptors that no later, smaller grid writes again.  (Every set makes at least one launch per batch:
+    num_batches >= 6 * NUM_SLOTS wraps them all; a sampler's and a table's set, two launches per batch, after 3.)"""
     gen_start = hip.SCAN_GEN_LIMIT - 5
-    fanouts = [5, 5] if kind == "random_walk" else [7, 5]
-    nseed, big = 300, 1200
+    fanouts = fanouts or ([5, 5] if kind == "random_walk" else [7, 5])
     d_indices, o_indices = dev(w.indices.copy()), w.indices.copy()
     sampler, ost, okw = _make_sampler(hip, oracle, w, kind, fanouts, big, d_indices)
     bt = sampler.new_batch()
@@ -117,11 +121,14 @@ def _drive_across_generation_wrap(hip, oracle, w, kind, ticket=-1):
     d_table = dev(w.table)
     oht = oracle.HashTable(w.num_node, sampler.max_nodes)
     rng = oracle.make_rng(oracle.RNG_PHILOX, SEED)
-    for b in range(NUM_BATCHES):
+    for b in range(num_batches):
         seeds = _seeds(big if b < 3 else nseed - b, w.num_node, seed=300 + b)
         sampler.run_batch(b, dev(seeds), 700 + b, bt, d_table)
         m = bt.wait()
-        want = oracle.do_sample(w.indptr, o_indices, seeds, fanouts, ost, rng, 700 + b, oht, **okw)
+        if kind == "khop_shared":
+            want = khop_shared_refs.reference_batch(w.indptr, o_indices, seeds, fanouts, SEED, 700 + b)
+        else:
+            want = oracle.do_sample(w.indptr, o_indices, seeds, fanouts, ost, rng, 700 + b, oht, **okw)
         _check_batch(hip, oracle, w, bt, m, want, 2, "%s batch %d" % (kind, b), with_data=kind == "random_walk")
         if b == 2:
             # still the old cycle (no set has made six launches yet), and the large grids have stamped it
