@@ -67,15 +67,15 @@ def _u32(t):
     return t.long() & 0xFFFFFFFF
 
 
-def _on_device(model, indptr, indices, feat, device):
+def _on_device(model, indptr, indices, feat, device, q8_ok=False):
     """(device, the model's dtype, indptr, indices, feat, N) with graph and features moved to `device` (default: the
-    model's)"""
+    model's).  q8_ok: the caller also reads a q8 feature table (uint8 [N, S], csrc/q8_rows.h)"""
     param = next(model.parameters())
     device = th.device(device) if device is not None else param.device
     dtype = param.dtype
     if isinstance(feat, np.ndarray):
         feat = th.from_numpy(feat)
-    assert feat.dtype in (th.float32, th.float16) or feat.dtype == dtype
+    assert feat.dtype in (th.float32, th.float16) or feat.dtype == dtype or (q8_ok and feat.dtype == th.uint8)
     indptr, indices, h = _as_ids(indptr, device), _as_ids(indices, device), feat.to(device)
     n = indptr.numel() - 1
     assert h.shape[0] == n
@@ -118,7 +118,8 @@ def _chunk_op_by_op(sage, h, indptr64, indices64, a, b, src_factor, dtype):
 def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=None):
     """[N, n_classes] fp32 logits of `model` (models.SAGE or models.GCN, fused or op-by-op layers) for every node of the
     graph (indptr, indices: the CSR, int32-viewed u32 tensors or u32 arrays; row v lists the nodes v aggregates from),
-    feat [N, D] fp32 or fp16.  (A float64 model computes and answers in float64, on the op-by-op path.)  device: where to compute (default: the model's); graph and features are moved there if
+    feat [N, D] fp32 or fp16, or a q8 table (uint8 [N, S]: the first layer's CSR aggregation reads the codes as they are,
+    fgnn_csr_aggregate_q8; GPU only).  (A float64 model computes and answers in float64, on the op-by-op path.)  device: where to compute (default: the model's); graph and features are moved there if
     they are elsewhere.  The model runs in eval() mode under no_grad -- no dropout -- and gets its training flag
     back."""
     if isinstance(model, models.PinSAGE):
@@ -130,9 +131,11 @@ def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=N
     if not isinstance(model, (models.SAGE, models.GCN)):
         raise NotImplementedError("layer-wise inference knows models.SAGE and models.GCN, not %s" % type(model).__name__)
     sage = isinstance(model, models.SAGE)
-    device, dtype, indptr, indices, h, n = _on_device(model, indptr, indices, feat, device)
+    device, dtype, indptr, indices, h, n = _on_device(model, indptr, indices, feat, device, q8_ok=True)
     assert batch_rows >= 1
     nn = _library() if device.type == "cuda" and dtype == th.float32 else None
+    if h.dtype == th.uint8 and nn is None:
+        raise NotImplementedError("a q8 feature table is read by the HIP kernels only: fp32 model on a GPU")
     was_training = model.training
     model.eval()
     try:
@@ -150,7 +153,7 @@ def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=N
                     h = h.contiguous()
             for li, layer in enumerate(model.layers):
                 W, bias = _layer_params(model, layer)
-                din = h.shape[1]
+                din = W.shape[1] // 2 if sage else W.shape[1]  # (not h.shape[1]: q8 rows are S bytes wide)
                 out = th.empty((n, W.shape[0]), dtype=th.float32 if nn else dtype, device=device)
                 for a in range(0, n, batch_rows):
                     b = min(a + batch_rows, n)
@@ -158,7 +161,10 @@ def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=N
                         z = _chunk_op_by_op(sage, h, indptr64, indices64, a, b, src_factor, dtype)
                     elif sage:
                         z = th.empty((b - a, 2 * din), dtype=th.float32, device=device)
-                        z[:, :din] = h[a:b]  # (fp16 features: only these rows are upcast)
+                        if h.dtype == th.uint8:  # q8 features: only these rows are decoded
+                            models.decode_q8(h[a:b], din, out=z[:, :din])
+                        else:
+                            z[:, :din] = h[a:b]  # (fp16 features: only these rows are upcast)
                         nn.csr_aggregate_into(z[:, din:], h, indptr, indices, first=a, count=b - a, dst_mode=2,
                                               max_edges=max_edges)
                     else:

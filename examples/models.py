@@ -98,13 +98,41 @@ def _half_rows_apply(block, h):
             and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32)
 
 
+def _q8_rows_apply(block, h):
+    """q8 input features (the engine's `feat_store_dtype = q8`: a uint8 [num_src, S] tensor, csrc/q8_rows.h) that the
+    first layer of the fused SAGE, GCN and PinSAGE models takes as they are -- the _half_rows_apply twin: the aggregation
+    kernels read the codes (fgnn_block_aggregate_ex_q8 / _scaled_q8, fgnn_sage_finish_z_q8), sums and everything behind
+    them are fp32.  A layer learns D from its own in_feats."""
+    return (_fused_aggregate is not None and h.is_cuda and h.dtype == th.uint8 and h.dim() == 2
+            and getattr(block.row, "dtype", None) == th.int32 and block.col.dtype == th.int32)
+
+
+def layer_in_feats(layer):
+    """D: the width of the rows a layer of this file takes"""
+    for name in ("in_feats", "fc", "fc_self", "Q"):
+        v = getattr(layer, name, None)
+        if v is not None:
+            return v if isinstance(v, int) else v.in_features
+    raise TypeError("no input width known for %s" % type(layer).__name__)
+
+
+def decode_q8(x, dim, out=None):
+    """fp32 [rows, dim] of q8 rows (into `out` if given): ONE launch (fgnn_dequantize_rows_q8); there is no decode off
+    the GPU"""
+    from fgnn_hip.lib import dequantize_rows_q8
+    return dequantize_rows_q8(x if x.stride(1) == 1 else x.contiguous(), dim, out=out)
+
+
 def input_rows(layer, block, x):
-    """what a model hands its first layer: x itself -- unless x is fp16 and the layer cannot read half rows (GAT, every
-    op-by-op layer, any layer off the GPU or without the HIP library): those get ONE torch upcast of the whole tensor,
-    num_src x D, which is what a half-precision store otherwise saves"""
-    if x.dtype != th.float16:
+    """what a model hands its first layer: x itself -- unless x is fp16 or q8 and the layer cannot read such rows (GAT,
+    every op-by-op layer, any layer off the GPU or without the HIP library): those get ONE upcast (torch) or decode
+    (fgnn_dequantize_rows_q8) of the whole tensor, num_src x D, which is what a narrower store otherwise saves"""
+    if x.dtype not in (th.float16, th.uint8):
         return x
-    if isinstance(layer, (FusedSAGEConv, FusedGraphConv, FusedWeightedSAGEConv)) and _half_rows_apply(block, x):
+    fused = isinstance(layer, (FusedSAGEConv, FusedGraphConv, FusedWeightedSAGEConv))
+    if x.dtype == th.uint8:
+        return x if fused and _q8_rows_apply(block, x) else decode_q8(x, layer_in_feats(layer))
+    if fused and _half_rows_apply(block, x):
         return x
     return x.float()
 
@@ -151,7 +179,7 @@ class _FusedSageFn(th.autograd.Function):
     def forward(ctx, h, weight, bias, block, num_dst):
         from fgnn_hip.nn import aggregate_into, sage_finish_z
         h = h.contiguous()
-        din = h.shape[1]
+        din = weight.shape[1] // 2  # (not h.shape[1]: q8 rows are S bytes wide)
         # z and the in-degree counts out of ONE zeroed buffer (one fill), the neighbour sums and the counts by one
         # launch, the mean's scaling and the copy of the destinations' own rows by one more (fgnn_sage_finish_z)
         buf = th.zeros(num_dst * (2 * din + 1), dtype=th.float32, device=h.device)  # (h may be fp16: upcast on load)
@@ -163,7 +191,7 @@ class _FusedSageFn(th.autograd.Function):
         else:
             inv = deg.clamp(min=1).reciprocal_()
             z[:, din:] *= inv.unsqueeze(1)
-            z[:, :din] = h[:num_dst]
+            z[:, :din] = h[:num_dst] if h.dtype != th.uint8 else decode_q8(h[:num_dst], din)
         ctx.save_for_backward(z, weight, block.row, block.col, inv)
         ctx.num_src = h.shape[0]
         return th.addmm(bias, z, weight.t())
@@ -227,7 +255,7 @@ class FusedSAGEConv(nn.Module):
 
     def forward(self, block, h):
         num_dst = block.number_of_dst_nodes()
-        if _fused_layers_apply(block, h) or _half_rows_apply(block, h):
+        if _fused_layers_apply(block, h) or _half_rows_apply(block, h) or _q8_rows_apply(block, h):
             return _FusedSageFn.apply(h, self.weight, self.bias, block, num_dst)
         agg = _sum_to_dst(block, h) / _in_degree(block, h.dtype).clamp(min=1).unsqueeze(1)
         return th.cat([h[:num_dst], agg], 1).mm(self.weight.t()) + self.bias
@@ -290,7 +318,8 @@ class _FusedGraphConvFn(th.autograd.Function):
         from fgnn_hip.nn import aggregate_scaled_into, block_degrees
         h = h.contiguous()
         src_deg, dst_deg = block_degrees(block.row, block.col, h.shape[0], num_dst)
-        agg = th.zeros((num_dst, h.shape[1]), dtype=th.float32, device=h.device)  # (h may be fp16: upcast on load)
+        # (h may be fp16, upcast on load, or q8 rows of S bytes: the layer's width is the weight's)
+        agg = th.zeros((num_dst, weight.shape[1]), dtype=th.float32, device=h.device)
         aggregate_scaled_into(agg, h, block.row, block.col, None, src_deg, 1, dst_deg, 1)
         ctx.save_for_backward(agg, weight, block.row, block.col, src_deg, dst_deg)
         ctx.num_src = h.shape[0]
@@ -317,7 +346,7 @@ class FusedGraphConv(GraphConv):
     it IS GraphConv."""
 
     def conv(self, block, h):
-        if _fused_layers_apply(block, h) or _half_rows_apply(block, h):
+        if _fused_layers_apply(block, h) or _half_rows_apply(block, h) or _q8_rows_apply(block, h):
             return _FusedGraphConvFn.apply(h, self.fc.weight, self.fc.bias, block, block.number_of_dst_nodes())
         return super().conv(block, h)
 
@@ -368,6 +397,8 @@ class FusedWeightedSAGEConv(WeightedSAGEConv):
     destinations' own rows go from the fp16 tensor straight into the concatenation."""
 
     def forward(self, block, h):
+        if _q8_rows_apply(block, h):  # q8 input features: the Q GEMM needs every row in fp32, so ONE decode serves both uses
+            h = decode_q8(h, self.Q.in_features)
         if not (_fused_layers_apply(block, h) or _half_rows_apply(block, h)):
             return super().forward(block, h)
         from fgnn_hip.nn import relu_l2norm

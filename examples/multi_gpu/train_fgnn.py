@@ -59,10 +59,12 @@ def build_parser():
     ap.add_argument("--num-train-worker", type=int, default=1)
     ap.add_argument("--single-gpu", action="store_true", help="all workers on cuda:0 (common_config.py:186-191)")
     ap.add_argument("--cache-policy", default="pre_sample", choices=list(sam.cache_policies))
-    ap.add_argument("--feat-store", default="f32", choices=["f32", "f16"],
+    ap.add_argument("--feat-store", default="f32", choices=["f32", "f16", "q8"],
                     help="f16: the engine keeps, caches and gathers the input features as IEEE binary16 rows "
                          "(config key feat_store_dtype; feat_f16.bin, written by --make-dataset or by `fgnn_dataset "
-                         "feat-f16`) and the fused models' first layer reads them as they are; compute stays fp32")
+                         "feat-f16`) and the fused models' first layer reads them as they are; compute stays fp32.  "
+                         "q8: 8-bit rows with a per-row scale / lo header (feat_q8.bin, `fgnn_dataset feat-q8`), read "
+                         "as they are by the same layers and decoded once for every other")
     ap.add_argument("--cache-percentage", type=float, default=0.0)
     ap.add_argument("--no-pipeline", action="store_true")
     ap.add_argument("--async", dest="async_train", action="store_true",
@@ -250,6 +252,7 @@ def make_dataset(args):
         synth.write_dataset(root, name, shape["num_node"], shape["num_edge"], shape["feat_dim"], shape["num_class"],
                             shape["num_train"], shape.get("num_valid", 1000), shape.get("num_test", 1000),
                             learnable=args.make_dataset == "learnable", feat_f16=args.feat_store == "f16",
+                            feat_q8=args.feat_store == "q8",
                             with_prefix=args.sample_type == "weighted_khop_prefix",
                             with_alias=args.sample_type in ("weighted_khop", "weighted_khop_hash_dedup"))
 

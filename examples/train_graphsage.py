@@ -72,10 +72,12 @@ def main():
     # GAT (example/samgraph/train_gat.py: 8 heads x 32 hidden, attention dropout = feature dropout)
     ap.add_argument("--num-heads", type=int, default=8, help="gat / gatv2: attention heads of the inner layers")
     ap.add_argument("--attn-drop", type=float, default=None, help="gat / gatv2: attention dropout (default: --dropout)")
-    ap.add_argument("--feat-store", default="f32", choices=["f32", "f16"],
+    ap.add_argument("--feat-store", default="f32", choices=["f32", "f16", "q8"],
                     help="f16: the engine keeps, caches and gathers the input features as IEEE binary16 rows "
                          "(config key feat_store_dtype; feat_f16.bin, written by --make-dataset or by `fgnn_dataset "
-                         "feat-f16`) and the fused models' first layer reads them as they are; compute stays fp32")
+                         "feat-f16`) and the fused models' first layer reads them as they are; compute stays fp32.  "
+                         "q8: 8-bit rows with a per-row scale / lo header (feat_q8.bin, `fgnn_dataset feat-q8`), read "
+                         "as they are by the same layers and decoded once for every other")
     ap.add_argument("--cache-policy", default="pre_sample",
                     help="a key of sam.cache_policies: pre_sample, presample_static, degree, ..., or dynamic_cache "
                          "(arch4 only: the cache is the previous batch's feature tensor; khop0 / khop1 / weighted_khop, "
@@ -91,7 +93,8 @@ def main():
         t0 = time.time()
         synth.write_dataset(root, name, shape["num_node"], shape["num_edge"], shape["feat_dim"], shape["num_class"],
                             shape["num_train"], shape.get("num_valid", 1000), shape.get("num_test", 1000),
-                            learnable=args.make_dataset == "learnable", feat_f16=args.feat_store == "f16")
+                            learnable=args.make_dataset == "learnable", feat_f16=args.feat_store == "f16",
+                            feat_q8=args.feat_store == "q8")
         print("dataset written in {:.1f}s".format(time.time() - t0))
 
     two = th.cuda.device_count() >= 2

@@ -111,8 +111,9 @@ void RunConfig::Parse(const char **keys, const char **vals, size_t n) {
   presample_epoch = raw.count("presample_epoch") ? std::stoi(raw["presample_epoch"]) : 0;
   if (raw.count("feat_store_dtype")) {
     const std::string &v = raw["feat_store_dtype"];
-    SAM_CHECK(v == "f32" || v == "f16") << "bad config value feat_store_dtype = " << v << " (f32 or f16)";
+    SAM_CHECK(v == "f32" || v == "f16" || v == "q8") << "bad config value feat_store_dtype = " << v << " (f32, f16 or q8)";
     feat_store_f16 = v == "f16";
+    feat_store_q8 = v == "q8";
   }
   if (raw.count("seed")) seed = std::stoull(raw["seed"], nullptr, 0);
   // environment

@@ -36,6 +36,9 @@ struct RunConfig {
   // feat_store_dtype (optional: f32, the default, or f16): the input features are stored, cached, gathered and handed
   // to the trainer as IEEE binary16 rows from feat_f16.bin -- half the bytes at every step that moves them
   bool feat_store_f16 = false;
+  // feat_store_dtype = q8: 8-bit rows with a per-row scale / lo header from feat_q8.bin (csrc/q8_rows.h): round_up(D, 16)
+  // + 16 bytes a row, handed to the trainer as uint8 rows of that width
+  bool feat_store_q8 = false;
   int omp_thread_num = 1;
   uint64_t seed = 0x5A4D47;
   bool is_configured = false;

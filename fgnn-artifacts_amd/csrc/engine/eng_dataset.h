@@ -23,8 +23,11 @@ struct Dataset {
   size_t feat_rows = 0;               // num_node, or 2^SAMGRAPH_EMPTY_FEAT
   // the feature table's element type and size, by the config key feat_store_dtype: FGNN_F32 / 4 (feat.bin), or
   // FGNN_F16 / 2 (feat_f16.bin, written by `fgnn_dataset feat-f16`); every gather, cache and batch buffer follows them
+  // FGNN_U8 / 1 (feat_q8.bin, `fgnn_dataset feat-q8`): q8 rows, whose stored width feat_row = round_up(feat_dim, 16) + 16
+  // elements differs from the logical feat_dim.  Bytes are sized, cached, gathered and queued by feat_row.
   int feat_dtype = FGNN_F32;
   size_t feat_esz = 4;
+  size_t feat_row = 0;  // elements of a stored row: feat_dim, or the bytes of a q8 row
   void Load(const RunConfig &rc);
 };
 

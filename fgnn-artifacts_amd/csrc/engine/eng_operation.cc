@@ -183,7 +183,7 @@ int samgraph_wait_one_child(void) {  // operation.cc:374-385
 const void *samgraph_torch_get_graph_feat_ptr(uint64_t key, size_t *num_rows, size_t *dim, int *dtype, int *device) {
   auto b = CurrentChecked(key);
   *num_rows = b->feat_rows;
-  *dim = Engine::Get().Data().feat_dim;
+  *dim = Engine::Get().Data().feat_row;  // the stored row width: feat_dim, or the bytes of a q8 row
   *dtype = Engine::Get().Data().feat_dtype;
   *device = b->device;
   return b->feat;
@@ -231,7 +231,7 @@ const uint32_t *samgraph_torch_get_graph_output_nodes_ptr(uint64_t key, size_t *
 const void *samgraph_torch_get_dataset_feat_ptr(size_t *num_rows, size_t *dim, int *dtype) {
   auto &d = Engine::Get().Data();
   *num_rows = d.feat_rows;
-  *dim = d.feat_dim;
+  *dim = d.feat_row;
   *dtype = d.feat_dtype;
   return d.feat.ptr;
 }

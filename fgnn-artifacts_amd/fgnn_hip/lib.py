@@ -115,6 +115,13 @@ SIGNATURES = {
     "fgnn_csr_aggregate_workspace_bytes": (_Z, (_Z, _Z, _Z)),
     "fgnn_csr_aggregate": (_I, (_P, _P, _P, _P, _Z, _Z, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P, _Z, _P)),
     "fgnn_csr_aggregate_f16": (_I, (_P, _P, _P, _P, _Z, _Z, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P, _Z, _P)),
+    "fgnn_q8_row_bytes": (_Z, (_Z,)),
+    "fgnn_quantize_rows_q8": (_I, (_P, _Z, _Z, _Z, _P, _Z, _P)),
+    "fgnn_dequantize_rows_q8": (_I, (_P, _Z, _P, _Z, _Z, _P, _Z, _P)),
+    "fgnn_block_aggregate_ex_q8": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _P)),
+    "fgnn_block_aggregate_scaled_q8": (_I, (_P, _P, _P, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P)),
+    "fgnn_sage_finish_z_q8": (_I, (_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P)),
+    "fgnn_csr_aggregate_q8": (_I, (_P, _P, _P, _P, _Z, _Z, _Z, _P, _Z, _Z, _P, _Z, _P, _I, _P, _I, _P, _Z, _P)),
     "fgnn_csr_gat_max_heads": (_Z, ()),
     "fgnn_csr_gat_workspace_bytes": (_Z, (_Z, _Z, _Z, _Z)),
     "fgnn_csr_gat_attention": (_I, (_P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _Z, _Z, _Z, _F, _P, _Z, _P, _Z, _P)),
@@ -657,6 +664,47 @@ def gather_rows(out, src, src_index=None, dst_index=None, n=None, d_n=None, src_
         return out
     _check(load().fgnn_gather_rows(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), n, _ptr(d_n), n, dim,
                                    _T2DT[out.dtype], _stream()), "fgnn_gather_rows")
+    return out
+
+
+# ---- 8-bit feature store (csrc/q8_rows.hip): a torch.uint8 [rows, S] tensor, S = q8_row_bytes(D), is q8 rows ----------
+
+def q8_row_bytes(dim):
+    """S: bytes of a q8 row of `dim` columns -- the codes rounded up to 16, plus the 16-byte header (fgnn_q8_row_bytes)"""
+    return int(load().fgnn_q8_row_bytes(dim))
+
+
+def is_q8_rows(h, dim):
+    """is `h` a tensor of q8 rows of `dim` columns: uint8 [rows, q8_row_bytes(dim)], unit stride inside a row?"""
+    return h.dtype == torch.uint8 and h.dim() == 2 and h.stride(1) == 1 and h.shape[1] == q8_row_bytes(dim)
+
+
+def quantize_rows_q8(x, out=None):
+    """q8 rows (uint8 [rows, S]) of the fp32 matrix x [rows, D] (unit stride inside a row): fgnn_quantize_rows_q8.  `out`:
+    a uint8 [rows, S] tensor to fill -- it may be a column block of a wider matrix -- else a new one."""
+    _need_gpu(x, out)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    rows, dim = x.shape
+    if out is None:
+        out = torch.empty((rows, q8_row_bytes(dim)), dtype=torch.uint8, device=x.device)
+    assert is_q8_rows(out, dim) and out.shape[0] == rows
+    _check(load().fgnn_quantize_rows_q8(_ptr(x), x.stride(0), rows, dim, _ptr(out), out.stride(0), _stream(x)),
+           "fgnn_quantize_rows_q8")
+    return out
+
+
+def dequantize_rows_q8(h, dim, index=None, out=None):
+    """fp32 [n, dim] = lo + scale * q of the q8 rows h[index] (index: int32-viewed u32 row ids; None: every row in
+    order): fgnn_dequantize_rows_q8.  `out`: an fp32 [n, dim] tensor to fill -- it may be a column block of a wider
+    matrix, the left half of a SAGE z for one -- else a new one."""
+    _need_gpu(h, index, out)
+    assert is_q8_rows(h, dim) and (index is None or (index.dtype == torch.int32 and index.is_contiguous()))
+    n = h.shape[0] if index is None else index.numel()
+    if out is None:
+        out = torch.empty((n, dim), dtype=torch.float32, device=h.device)
+    assert out.dtype == torch.float32 and out.shape == (n, dim) and out.stride(1) == 1
+    _check(load().fgnn_dequantize_rows_q8(_ptr(h), h.stride(0), _ptr(index), n, dim, _ptr(out), out.stride(0),
+                                          _stream(h)), "fgnn_dequantize_rows_q8")
     return out
 
 

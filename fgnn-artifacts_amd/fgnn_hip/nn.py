@@ -13,18 +13,32 @@ from . import lib as _lib
 _ptr, _st = _lib._ptr, _lib._stream
 
 
+def _rows_match(h, out):
+    """h holds one row of out.shape[1] columns per source: fp32 / fp16 elements, or q8 rows"""
+    return _lib.is_q8_rows(h, out.shape[1]) if h.dtype == torch.uint8 else out.shape[1] == h.shape[1]
+
+
+_ROW_DTYPES = (torch.float32, torch.float16, torch.uint8)
+
+
 def _aggregate(out, h, src_idx, dst_idx, weight, in_degree=None, scaling=None):
     """the one aggregation call: out[dst_idx[e]] += weight[e] * h[src_idx[e]] through fgnn_block_aggregate_ex (h
     contiguous; in_degree optional), or, with scaling = (src_deg, src_mode, dst_deg, dst_mode), through
     fgnn_block_aggregate_scaled (h with a row stride, degree factors inside).  h float16 (input features of a
-    half-precision store): the _f16 twin of either, which upcasts the rows on load."""
+    half-precision store): the _f16 twin of either, which upcasts the rows on load.  h uint8 (q8 rows of an 8-bit
+    store, out.shape[1] columns each): the _q8 twin, which reads the codes as they are (h's row stride in bytes)."""
     L = _lib.load()
     n, dim = src_idx.numel(), h.shape[1]
-    f16 = "_f16" if h.dtype == torch.float16 else ""
+    q8 = h.dtype == torch.uint8
+    f16 = "_q8" if q8 else ("_f16" if h.dtype == torch.float16 else "")
+    if q8:
+        dim = out.shape[1]
+        assert _lib.is_q8_rows(h, dim), "uint8 rows of %d bytes are not q8 rows of %d columns" % (h.shape[1], dim)
     if scaling is None:
         what = "fgnn_block_aggregate_ex" + f16
-        code = getattr(L, what)(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, _ptr(h), dim, _ptr(out),
-                                out.stride(0), _ptr(in_degree), _st(h))
+        rows = (_ptr(h), h.stride(0), dim) if q8 else (_ptr(h), dim)  # the q8 entry point takes a row stride
+        code = getattr(L, what)(_ptr(src_idx), _ptr(dst_idx), _ptr(weight), n, *rows, _ptr(out), out.stride(0),
+                                _ptr(in_degree), _st(h))
     else:
         src_deg, src_mode, dst_deg, dst_mode = scaling
         what = "fgnn_block_aggregate_scaled" + f16
@@ -71,9 +85,10 @@ def aggregate_into(out, h, src_idx, dst_idx, edge_weight=None, in_degree=None):
     """out[dst_idx[e]] += edge_weight[e] * h[src_idx[e]] into a caller-initialised fp32 tensor: no autograd, for layers
     that write their own backward (examples/models.py: FusedSAGEConv).  `out` may be a column block of a wider
     row-major matrix (unit stride inside a row); in_degree (fp32 [num_dst], caller-zeroed) receives the edge count of
-    every destination on the way.  h: fp32, or fp16 rows that are upcast on load."""
-    assert h.dtype in (torch.float32, torch.float16) and out.dtype == torch.float32 and h.is_contiguous()
-    assert out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
+    every destination on the way.  h: fp32, fp16 rows that are upcast on load, or q8 rows (uint8 [num_src, S], which may
+    be a column block of a wider uint8 matrix) that are read as they are."""
+    assert h.dtype in _ROW_DTYPES and out.dtype == torch.float32 and (h.is_contiguous() or h.dtype == torch.uint8)
+    assert out.dim() == 2 and out.stride(1) == 1 and _rows_match(h, out)
     assert src_idx.dtype == torch.int32 and dst_idx.dtype == torch.int32
     return _aggregate(out, h, src_idx, dst_idx, edge_weight, in_degree)
 
@@ -83,11 +98,11 @@ def aggregate_into(out, h, src_idx, dst_idx, edge_weight=None, in_degree=None):
 # graph (examples/graphed_step.py), where a node costs the GPU 15-20 us whatever it does.
 
 def sage_finish_z(z, h, deg, num_dst, din):
-    """z[:, :din] = h[:num_dst] (h fp32, or fp16 and upcast); inv = 1 / max(deg, 1); z[:, din:] *= inv.  Returns inv
-    (fp32 [num_dst])."""
-    assert h.dtype in (torch.float32, torch.float16)
+    """z[:, :din] = h[:num_dst] (h fp32, fp16 and upcast, or q8 rows of din columns and decoded); inv = 1 / max(deg, 1);
+    z[:, din:] *= inv.  Returns inv (fp32 [num_dst])."""
+    assert h.dtype in _ROW_DTYPES and (h.dtype != torch.uint8 or _lib.is_q8_rows(h, din))
     inv = torch.empty(num_dst, dtype=torch.float32, device=z.device)
-    what = "fgnn_sage_finish_z" + ("_f16" if h.dtype == torch.float16 else "")
+    what = "fgnn_sage_finish_z" + {torch.float16: "_f16", torch.uint8: "_q8"}.get(h.dtype, "")
     _lib._check(getattr(_lib.load(), what)(_ptr(z), z.stride(0), _ptr(h), h.stride(0), _ptr(deg), _ptr(inv), num_dst, din,
                                            _st(z)), what)
     return inv
@@ -157,10 +172,10 @@ def aggregate_scaled_into(out, h, src_idx, dst_idx, edge_weight=None, src_deg=No
     """out[dst_idx[e]] += f_dst(dst_deg[dst_idx[e]]) * edge_weight[e] * f_src(src_deg[src_idx[e]]) * h[src_idx[e]] into a
     caller-initialised fp32 tensor, no autograd (modes: 0 factor 1, 1 rsqrt(max(d, 1)), 2 1 / max(d, 1)).  `out` AND `h`
     may be column blocks of wider row-major matrices (unit stride inside a row).  The backward pass of a layer is the
-    same call with the index tensors, the degree vectors and the modes swapped.  h: fp32, or fp16 rows that are upcast
-    on load."""
-    assert h.dtype in (torch.float32, torch.float16) and out.dtype == torch.float32
-    assert h.dim() == 2 and h.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
+    same call with the index tensors, the degree vectors and the modes swapped.  h: fp32, fp16 rows that are upcast
+    on load, or q8 rows that are read as they are."""
+    assert h.dtype in _ROW_DTYPES and out.dtype == torch.float32
+    assert h.dim() == 2 and h.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and _rows_match(h, out)
     assert src_idx.dtype == torch.int32 and dst_idx.dtype == torch.int32
     assert src_idx.is_contiguous() and dst_idx.is_contiguous() and src_idx.numel() == dst_idx.numel()
     for t in (edge_weight, src_deg, dst_deg):
@@ -199,14 +214,15 @@ def csr_aggregate_into(out, h, indptr, indices, nodes=None, first=0, count=None,
                        src_mode=0, dst_deg=None, dst_mode=0, max_edges=None):
     """out[i] = f_dst(v) * sum over v's CSR row of edge_weight[p] * f_src(indices[p]) * h[indices[p]] for v = nodes[i], or
     v = first + i for i < count (default: out's rows): fgnn_csr_aggregate, no autograd.  out (fp32) is OVERWRITTEN --
-    no zero fill, rows without a neighbour become zeros --, h is fp32 or fp16 (upcast on load); both may be column blocks
+    no zero fill, rows without a neighbour become zeros --, h is fp32, fp16 (upcast on load) or q8 rows (read as they are;
+    its own order of additions, the same promise); both may be column blocks
     of wider row-major matrices.  indptr / indices: the int32-viewed u32 CSR tensors the engine uses; edge_weight fp32
     per CSR entry; src_deg / dst_deg fp32 per NODE with the modes of aggregate_scaled_into, dst_deg=None with a
     dst_mode taking the row's own length.  No float atomics: a row's bits depend on the row alone, whatever else the
     call computes.  max_edges: upper bound of the summed lengths of the call's rows (default: the graph's edge count,
     which holds unless `nodes` repeats ids; rows beyond the bound are still right, only summed by one wave each)."""
-    assert h.dtype in (torch.float32, torch.float16) and out.dtype == torch.float32
-    assert h.dim() == 2 and h.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and out.shape[1] == h.shape[1]
+    assert h.dtype in _ROW_DTYPES and out.dtype == torch.float32
+    assert h.dim() == 2 and h.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and _rows_match(h, out)
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32
     assert indptr.is_contiguous() and indices.is_contiguous()
     for t in (edge_weight, src_deg, dst_deg):
@@ -219,11 +235,11 @@ def csr_aggregate_into(out, h, indptr, indices, nodes=None, first=0, count=None,
         count = out.shape[0]
     assert out.shape[0] >= count and (nodes is not None or first + count <= indptr.numel() - 1)
     _lib._need_gpu(out, h, indptr, indices, nodes, edge_weight, src_deg, dst_deg)
-    dim = h.shape[1]
+    dim = out.shape[1]
     if max_edges is None:
         max_edges = indices.numel()
     ws, nbytes = csr_workspace(h.device, count, max_edges, dim)
-    what = "fgnn_csr_aggregate" + ("_f16" if h.dtype == torch.float16 else "")
+    what = "fgnn_csr_aggregate" + {torch.float16: "_f16", torch.uint8: "_q8"}.get(h.dtype, "")
     code = getattr(_lib.load(), what)(_ptr(indptr), _ptr(indices), _ptr(edge_weight), _ptr(nodes), first, count,
                                       max_edges, _ptr(h), h.stride(0), dim, _ptr(out), out.stride(0), _ptr(src_deg),
                                       src_mode, _ptr(dst_deg), dst_mode, _ptr(ws), nbytes, _st(h))

@@ -129,12 +129,34 @@ def learnable_labels(indptr, indices, feat, num_class, seed=5):
     return np.argmax((feat.astype(np.float64) + mean) @ proj, axis=1).astype(np.uint64)
 
 
+def q8_rows(feat):
+    """uint8 [N, S], S = round_up(D, 16) + 16: the fp32 matrix feat [N, D] as q8 rows (csrc/q8_rows.h) -- D codes, zeros,
+    then scale and lo (fp32) and eight zero bytes.  The encode of `fgnn_dataset feat-q8` and fgnn_quantize_rows_q8 in
+    numpy float32 operations in their order: scale = (hi - lo) / 255, inv = 255 / (hi - lo), q = clip(rint((x - lo) *
+    inv), 0, 255); a flat row: scale 0, codes 0."""
+    feat = np.ascontiguousarray(feat, dtype=np.float32)
+    n, dim = feat.shape
+    S = (dim + 15) // 16 * 16 + 16
+    lo, hi = feat.min(axis=1, keepdims=True), feat.max(axis=1, keepdims=True)
+    span = hi - lo
+    flat = span == 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scale = np.where(flat, np.float32(0), span / np.float32(255))
+        inv = np.where(flat, np.float32(0), np.float32(255) / span)
+    rows = np.zeros((n, S), dtype=np.uint8)
+    rows[:, :dim] = np.clip(np.rint((feat - lo) * inv), 0, 255).astype(np.uint8)
+    rows[:, S - 16:S - 12] = scale.astype(np.float32).view(np.uint8)
+    rows[:, S - 12:S - 8] = lo.view(np.uint8)
+    return rows
+
+
 def write_dataset(root, name, num_node, num_edge, feat_dim, num_class, num_train, num_valid=0, num_test=0,
-                  seed=42, with_prefix=False, with_alias=False, learnable=False, feat_f16=False):
+                  seed=42, with_prefix=False, with_alias=False, learnable=False, feat_f16=False, feat_q8=False):
     """Writes <root>/<name>/{meta.txt,indptr.bin,indices.bin,feat.bin,label.bin,*_set.bin}.  learnable: labels that
     follow from the features and the graph (learnable_labels) instead of uniform random ones.  feat_f16: also
     feat_f16.bin, the table of the engine's `feat_store_dtype = f16` (feat.bin rounded to IEEE binary16 -- what
-    `fgnn_dataset feat-f16` writes)."""
+    `fgnn_dataset feat-f16` writes).  feat_q8: also feat_q8.bin, the table of `feat_store_dtype = q8` (q8_rows of
+    feat.bin -- what `fgnn_dataset feat-q8` writes)."""
     d = os.path.join(root, name)
     os.makedirs(d, exist_ok=True)
     indptr, indices = powerlaw_csr(num_node, num_edge, seed)
@@ -148,6 +170,8 @@ def write_dataset(root, name, num_node, num_edge, feat_dim, num_class, num_train
     feat.tofile(os.path.join(d, "feat.bin"))
     if feat_f16:
         feat.astype(np.float16).tofile(os.path.join(d, "feat_f16.bin"))
+    if feat_q8:
+        q8_rows(feat).tofile(os.path.join(d, "feat_q8.bin"))
     random_labels = rng.integers(0, num_class, size=num_node, dtype=np.uint64)  # (drawn either way: same sets below)
     (learnable_labels(indptr, indices, feat, num_class) if learnable else random_labels).tofile(
         os.path.join(d, "label.bin"))

@@ -475,6 +475,51 @@ int fgnn_csr_aggregate_f16(const uint32_t *indptr, const uint32_t *indices, cons
                            size_t h_ld, size_t dim, float *out, size_t out_ld, const float *src_deg, int src_mode,
                            const float *dst_deg, int dst_mode, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- 8-bit feature store (csrc/q8_rows.hip; `feat_store_dtype = q8`) ---------------------------------------------------
+ * A q8 row of dim columns occupies S = fgnn_q8_row_bytes(dim) = round_up(dim, 16) + 16 bytes: dim unsigned 8-bit codes
+ * q_j, zeros up to S - 16, then the header -- scale (fp32), lo (fp32), eight zero bytes -- and stands for
+ * x^_j = lo + scale * q_j.  In every entry point below `h` (or `out` of the quantiser) points at such rows: a 16-byte
+ * aligned base, a row stride h_ld in BYTES that is a multiple of 16 and at least S.  Anything else -- and whatever the
+ * fp32 twin of an entry point refuses -- returns FGNN_EINVAL before any launch; a zero size returns FGNN_OK. */
+size_t fgnn_q8_row_bytes(size_t dim);
+/* Encode of fp32 rows x [num_rows, dim] (row stride x_ld elements), one wave per row, in fp32 IEEE operations in this
+ * order: lo = min_j x_j, hi = max_j x_j; hi == lo: scale = 0 and every code 0; otherwise scale = (hi - lo) / 255,
+ * inv = 255 / (hi - lo), q_j = min(255, max(0, rint((x_j - lo) * inv))), rounding to nearest even.  Every byte of
+ * [0, S) of an output row is written, nothing beyond.  Inputs are finite; for a non-finite input the codes are clamped
+ * and every access stays in bounds, nothing more is promised. */
+int fgnn_quantize_rows_q8(const float *x, size_t x_ld, size_t num_rows, size_t dim, void *out, size_t out_ld,
+                          void *stream);
+/* out[i, j] = lo + scale * q_j of row index[i] (index NULL: row i), fp32 [num_rows, dim] with a row stride of out_ld
+ * elements: one fp32 multiply and one fp32 add per element, each rounded on its own (not fused).  With out_ld = 2 dim it
+ * fills the left half of a SAGE z. */
+int fgnn_dequantize_rows_q8(const void *h, size_t h_ld, const uint32_t *index, size_t num_rows, size_t dim, float *out,
+                            size_t out_ld, void *stream);
+/* fgnn_block_aggregate_ex and fgnn_block_aggregate_scaled over q8 rows, read as they are: per edge a = w f_src scale
+ * and b = w f_src lo, per column one fma(a, q_j, acc_j), b summed once per edge and added to every column when a
+ * segment is flushed; weights, degree vectors, sums and out stay fp32.  Against the float64 sum over the decoded rows
+ * every output stays within (2 k + 8) 2^-23 of the sum of its terms' magnitudes |w f scale q| and |w f lo| (times the
+ * destination factor), k = the destination's edge count. */
+int fgnn_block_aggregate_ex_q8(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
+                               size_t num_edge, const void *h, size_t h_ld, size_t dim, float *out, size_t out_ld,
+                               float *in_degree, void *stream);
+int fgnn_block_aggregate_scaled_q8(const uint32_t *src_index, const uint32_t *dst_index, const float *edge_weight,
+                                   size_t num_edge, const void *h, size_t h_ld, size_t dim, float *out, size_t out_ld,
+                                   const float *src_deg, int src_mode, const float *dst_deg, int dst_mode,
+                                   void *stream);
+/* fgnn_sage_finish_z with q8 rows in h: z[i, :din] = the decode of h[i] (as fgnn_dequantize_rows_q8 computes it),
+ * inv[i] = 1 / max(deg[i], 1), z[i, din:] *= inv[i].  din % 4 == 0, 16-byte aligned rows of z. */
+int fgnn_sage_finish_z_q8(float *z, size_t ld, const void *h, size_t h_ld, const float *deg, float *inv, size_t num_dst,
+                          size_t din, void *stream);
+/* fgnn_csr_aggregate over q8 rows: the same contract, workspace (fgnn_csr_aggregate_workspace_bytes) and promise -- no
+ * float atomics, out overwritten, a row's bits depend on the row's content and dim only -- with an order of its own:
+ * edge i of a piece of fgnn_csr_split_length() edges goes to group i mod 4 of the owner wave, a group adds its edges in
+ * CSR order from 0, the four group sums combine as (g0 + g1) + (g2 + g3), the pieces in piece order from 0, and the
+ * destination factor multiplies once.  The error bound is the one of fgnn_block_aggregate_ex_q8. */
+int fgnn_csr_aggregate_q8(const uint32_t *indptr, const uint32_t *indices, const float *edge_weight,
+                          const uint32_t *nodes, size_t first, size_t num_rows, size_t max_edges, const void *h,
+                          size_t h_ld, size_t dim, float *out, size_t out_ld, const float *src_deg, int src_mode,
+                          const float *dst_deg, int dst_mode, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- GAT attention over whole CSR rows (csrc/csr_gat_attention.hip; exact layer-wise GAT inference:
  * examples/inference.py gat_layerwise_inference) ---------------------------------------------------------------------------
  * num_head heads H of num_feat features F.  For output row i < num_rows, with v = nodes ? nodes[i] : first + i and the

@@ -14,6 +14,9 @@
 //                                                           nearest even; the table of `feat_store_dtype = f16`).  Prints
 //                                                           how many finite values became infinite; fails if any did,
 //                                                           unless --allow-inf
+//   fgnn_dataset feat-q8           <dir>                 -> feat_q8.bin (N rows of round_up(D, 16) + 16 bytes from feat.bin:
+//                                                           8-bit codes and a per-row scale / lo header; the table of
+//                                                           `feat_store_dtype = q8`, the format of csrc/q8_rows.h)
 //   fgnn_dataset check             <dir>                 -> validates meta.txt against the CSR files
 //
 // What each file must contain follows the reference's generators (utility/data-process/toolkit/cache/
@@ -26,6 +29,7 @@
 //
 // Build: g++ -O2 -std=c++17 -fopenmp -o tools/dataset/fgnn_dataset tools/dataset/fgnn_dataset.cc
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -489,12 +493,64 @@ int FeatF16(std::string dir, bool allow_inf) {
   return 0;
 }
 
+// One q8 row (csrc/q8_rows.h): dim codes, zeros up to S - 16, then scale, lo and eight zero bytes; S = round_up(dim, 16)
+// + 16.  The encode in fp32 IEEE operations in the kernel's order (fgnn_quantize_rows_q8), so that the file and the GPU
+// agree bit for bit: scale = (hi - lo) / 255, inv = 255 / (hi - lo), q = min(255, max(0, rint((x - lo) * inv))), round to
+// nearest even; a flat row: scale 0, codes 0.  A NaN is skipped by min / max and encodes as 0, an infinity clamps.
+void EncodeQ8Row(const float *x, size_t dim, size_t S, unsigned char *row) {
+  float lo = INFINITY, hi = -INFINITY;
+  for (size_t j = 0; j < dim; ++j) lo = std::fmin(lo, x[j]), hi = std::fmax(hi, x[j]);
+  const bool flat = hi == lo;
+  const float range = hi - lo;
+  const float scale = flat ? 0.0f : range / 255.0f, inv = flat ? 0.0f : 255.0f / range;
+  std::memset(row, 0, S);
+  for (size_t j = 0; j < dim; ++j) {
+    const float d = x[j] - lo;
+    const float p = d * inv;
+    row[j] = (unsigned char)std::fmin(255.0f, std::fmax(0.0f, std::nearbyintf(p)));
+  }
+  std::memcpy(row + S - 16, &scale, 4);
+  std::memcpy(row + S - 12, &lo, 4);
+}
+
+// feat.bin (f32 [N x D]) -> feat_q8.bin (N rows of S bytes), a bounded slice of rows at a time
+int FeatQ8(std::string dir) {
+  if (dir.empty() || dir.back() != '/') dir += '/';
+  const auto meta = ReadMeta(dir);
+  const size_t num_node = meta.at("NUM_NODE"), dim = meta.at("FEAT_DIM");
+  if (dim == 0) Die("FEAT_DIM is 0");
+  const size_t S = ((dim + 15) & ~(size_t)15) + 16;
+  std::ifstream in(dir + "feat.bin", std::ios::binary | std::ios::ate);
+  if (!in) Die("cannot open " + dir + "feat.bin");
+  if ((size_t)in.tellg() != num_node * dim * 4) Die(dir + "feat.bin: expected " + std::to_string(num_node * dim * 4) + " bytes, found " + std::to_string((size_t)in.tellg()));
+  in.seekg(0);
+  const std::string path = dir + "feat_q8.bin";
+  std::ofstream out(path, std::ios::binary | std::ios::trunc);
+  if (!out) Die("cannot write " + path);
+  const size_t slice_rows = std::max<size_t>(1, ((size_t)1 << 22) / dim);  // about 16 MB in
+  std::vector<float> src(std::min(num_node, slice_rows) * dim);
+  std::vector<unsigned char> dst(std::min(num_node, slice_rows) * S);
+  for (size_t base = 0; base < num_node; base += slice_rows) {
+    const size_t n = std::min(slice_rows, num_node - base);
+    in.read(reinterpret_cast<char *>(src.data()), (std::streamsize)(n * dim * 4));
+    if (!in) Die("short read from " + dir + "feat.bin");
+#pragma omp parallel for
+    for (size_t i = 0; i < n; ++i) EncodeQ8Row(src.data() + i * dim, dim, S, dst.data() + i * S);
+    out.write(reinterpret_cast<const char *>(dst.data()), (std::streamsize)(n * S));
+  }
+  out.close();
+  if (!out) Die("cannot write " + path);
+  printf("wrote %s (%zu rows of %zu bytes)\n", path.c_str(), num_node, S);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
-  if (argc < 3) Die("usage: fgnn_dataset <cache-by-degree|cache-by-random|cache-by-heuristic|cache-by-degree-hop|cache-by-fake-optimal|32to64|prob-prefix-table|alias-table|coo-to-dataset|feat-f16|check> <dir> [arg]");
+  if (argc < 3) Die("usage: fgnn_dataset <cache-by-degree|cache-by-random|cache-by-heuristic|cache-by-degree-hop|cache-by-fake-optimal|32to64|prob-prefix-table|alias-table|coo-to-dataset|feat-f16|feat-q8|check> <dir> [arg]");
   const std::string cmd = argv[1];
   if (cmd == "feat-f16") return FeatF16(argv[2], argc > 3 && std::string(argv[3]) == "--allow-inf");
+  if (cmd == "feat-q8") return FeatQ8(argv[2]);
   if (cmd == "coo-to-dataset") {
     if (argc < 4) Die("coo-to-dataset needs <dir> <coo.bin>");
     return CooToDataset(argv[2], argv[3]);

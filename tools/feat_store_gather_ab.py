@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The feature gather of one papers100M-shaped batch (302 K rows of 128 features out of a table in HBM) with fp32 rows
-against fp16 rows (`feat_store_dtype = f16`): fgnn_gather_rows alone, interleaved alternations of the two in one
-process, median and spread of --ab rounds of --steps launches each, against the bytes each moves.
+against fp16 rows (`feat_store_dtype = f16`) and q8 rows (`= q8`: uint8 rows of round_up(dim, 16) + 16 bytes):
+fgnn_gather_rows alone, interleaved alternations of the three in one process, median and spread of --ab rounds of --steps launches each, against the bytes each moves.
 usage: feat_store_gather_ab.py [--rows 302000] [--dim 128] [--table-rows 20000000] [--ab 5] [--steps 200]"""
 import argparse
 import os
@@ -28,6 +28,9 @@ tables, outs = {}, {}
 for name, dt in (("f32", torch.float32), ("f16", torch.float16)):
     tables[name] = torch.empty((args.table_rows, args.dim), dtype=dt, device=dev).normal_()
     outs[name] = torch.empty((args.rows, args.dim), dtype=dt, device=dev)
+S = lib.q8_row_bytes(args.dim)  # the gather moves opaque bytes: any content serves
+tables["q8"] = torch.randint(0, 256, (args.table_rows, S), dtype=torch.uint8, device=dev)
+outs["q8"] = torch.empty((args.rows, S), dtype=torch.uint8, device=dev)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
 
@@ -47,12 +50,13 @@ for _ in range(args.ab):
     for name in tables:
         us[name].append(run(name, args.steps))
 for name, v in us.items():
-    mb = args.rows * args.dim * tables[name].element_size() / 1e6
+    mb = args.rows * tables[name].shape[1] * tables[name].element_size() / 1e6
     med = statistics.median(v)
     print("%s rows: median %.1f us per gather, min %.1f, max %.1f, spread %.1f; %.1f MB read + %.1f MB written = "
           "%.0f GB/s  (%s)" % (name, med, min(v), max(v), max(v) - min(v), mb, mb, 2 * mb / med * 1e3,
                                " ".join("%.1f" % t for t in v)))
-gain = statistics.median(us["f32"]) - statistics.median(us["f16"])
 spread = max(max(v) - min(v) for v in us.values())
-print("f32 median - f16 median = %.1f us, larger spread %.1f us: f16 %s"
-      % (gain, spread, "FASTER" if gain > spread else "NOT FASTER beyond the spread"))
+for slow, fast in (("f32", "f16"), ("f16", "q8")):
+    gain = statistics.median(us[slow]) - statistics.median(us[fast])
+    print("%s median - %s median = %.1f us, larger spread %.1f us: %s %s"
+          % (slow, fast, gain, spread, fast, "FASTER" if gain > spread else "NOT FASTER beyond the spread"))

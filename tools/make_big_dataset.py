@@ -2,10 +2,11 @@
 """Writes a papers100M-/products-shaped synthetic dataset in the engine's on-disk layout WITHOUT feat.bin (run the
 engine with SAMGRAPH_EMPTY_FEAT=k, like the reference's papers100M_empty): the CSR comes from bench.py's GPU generator,
 so a 1.6 G-edge graph is written in seconds.
-usage: make_big_dataset.py <dir> [papers100M|products|twitter|uk-2006-05] [--prefix] [--feat-f16]   (--prefix: also
+usage: make_big_dataset.py <dir> [papers100M|products|twitter|uk-2006-05] [--prefix] [--feat-f16] [--feat-q8]   (--prefix: also
 prob_prefix_table.bin for the weighted_khop_prefix sampler; --feat-f16: also feat_f16.bin, standard-normal features
 as IEEE binary16 for runs with `feat_store_dtype = f16` and real rows -- half the 57 GB an fp32 table of the papers100M
-shape would take)"""
+shape would take; --feat-q8: also feat_q8.bin, standard-normal features quantised on the GPU to the q8 rows of
+`feat_store_dtype = q8`, csrc/q8_rows.h -- 144 bytes a row at 128 columns)"""
 import os
 import sys
 
@@ -51,6 +52,14 @@ if "--feat-f16" in sys.argv:
             n = min(rows, w["num_node"] - a)
             x = torch.randn((n, w["feat_dim"]), generator=g, device=dev, dtype=torch.float32)
             f.write(x.cpu().numpy().astype(np.float16).tobytes())
+if "--feat-q8" in sys.argv:
+    from fgnn_hip import lib  # noqa: E402
+    rows = max(1, (1 << 26) // w["feat_dim"])  # 256 MB of fp32 at a time
+    with open(os.path.join(out, "feat_q8.bin"), "wb") as f:
+        for a in range(0, w["num_node"], rows):
+            n = min(rows, w["num_node"] - a)
+            x = torch.randn((n, w["feat_dim"]), generator=g, device=dev, dtype=torch.float32)
+            f.write(lib.quantize_rows_q8(x).cpu().numpy().tobytes())
 with open(os.path.join(out, "meta.txt"), "w") as f:
     f.write(f"NUM_NODE {w['num_node']}\nNUM_EDGE {ne}\nFEAT_DIM {w['feat_dim']}\nNUM_CLASS {w['num_class']}\n"
             f"NUM_TRAIN_SET {n_tr}\nNUM_VALID_SET 1000\nNUM_TEST_SET 1000\n")
