@@ -9,6 +9,10 @@ result is bit for bit the same whatever chunk it is computed in.  Per chunk of `
            row length as the degree), then ONE addmm with [W_self | W_neigh]
     GCN    agg = in_deg^-1/2 * sum out_deg^-1/2 h[u]      out_deg = a node's occurrences in `indices`, computed once per
            call; in_deg = the row length; then one addmm; ReLU between layers
+A pool SAGE (models.SAGE(aggregator="pool")) is not a mean model although its layers have fc_self / fc_neigh too: per
+layer p = relu(fc_pool(h)) for all nodes in chunks, the row maxima over the CSR rows by a torch scatter amax (on the CPU
+and on the GPU alike), then the layer's GEMM on z = [h[a:b] | max].  A CSR max kernel with the hub queue of csr_queue.h
+is the natural follow-up and is not built.
 On CPU tensors, or without the kernel library, the same function runs op by op in torch: what the CPU tests exercise
 and what the fused path is compared with.  Intermediate activations are fp32 [N, hidden] on the device; fp16 features
 are read as they are by the first layer (no fp32 copy of the feature matrix is made).
@@ -93,9 +97,29 @@ def _layer_params(model, layer):
     """(W [out, k in], bias) of a layer in the fused layout: SAGE [W_self | W_neigh], GCN fc"""
     if isinstance(model, models.GCN):
         return layer.fc.weight, layer.fc.bias
-    if isinstance(layer, models.FusedSAGEConv):
+    if isinstance(layer, (models.FusedSAGEConv, models.FusedSAGEPoolConv)):
         return layer.weight, layer.bias
     return th.cat([layer.fc_self.weight, layer.fc_neigh.weight], 1), layer.fc_neigh.bias
+
+
+def _pool_rows(layer, h, indptr64, indices64, n, batch_rows, dtype):
+    """the max-pooling half of a pool SAGE layer for all n nodes, [n, din]: p = relu(fc_pool(h)) in chunks of batch_rows
+    (fp16 / q8 rows upcast or decoded per chunk: fc_pool is a GEMM), then per chunk of destination rows the maxima over
+    their CSR rows by one torch scatter amax into zeros (a row without a neighbour keeps 0) -- on the CPU and on the GPU
+    alike.  That scatter materialises the chunk's p[src] rows: a CSR max kernel with the hub queue of csr_queue.h is the
+    natural follow-up and is not built."""
+    din = layer.fc_pool.in_features
+    p = th.empty((n, din), dtype=dtype, device=h.device)
+    for a in range(0, n, batch_rows):
+        b = min(a + batch_rows, n)
+        x = models.decode_q8(h[a:b], din) if h.dtype == th.uint8 else h[a:b].to(dtype)
+        p[a:b] = th.relu_(layer.fc_pool(x))
+    m = th.zeros((n, din), dtype=dtype, device=h.device)
+    for a in range(0, n, batch_rows):
+        b = min(a + batch_rows, n)
+        src, dst = _chunk_edges(indptr64, indices64, a, b)
+        m[a:b].scatter_reduce_(0, dst.unsqueeze(1).expand(-1, din), p[src], "amax", include_self=True)
+    return m
 
 
 def _chunk_op_by_op(sage, h, indptr64, indices64, a, b, src_factor, dtype):
@@ -131,6 +155,7 @@ def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=N
     if not isinstance(model, (models.SAGE, models.GCN)):
         raise NotImplementedError("layer-wise inference knows models.SAGE and models.GCN, not %s" % type(model).__name__)
     sage = isinstance(model, models.SAGE)
+    pool = sage and getattr(model, "aggregator", "mean") == "pool"  # a pool layer has fc_self / fc_neigh too: not a mean
     device, dtype, indptr, indices, h, n = _on_device(model, indptr, indices, feat, device, q8_ok=True)
     assert batch_rows >= 1
     nn = _library() if device.type == "cuda" and dtype == th.float32 else None
@@ -145,9 +170,9 @@ def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=N
             if not sage:  # GCN: out-degree = occurrences in indices, once per graph (not the hot path)
                 src_deg = th.bincount(_u32(indices), minlength=n).to(th.float32 if nn else dtype)
                 src_factor = src_deg.clamp(min=1).pow(-0.5)
-            if nn is None:
+            if nn is None or pool:
                 indices64 = _u32(indices)
-            else:
+            if nn is not None:
                 max_edges = _longest_chunk(indptr64, n, batch_rows, device)
                 if h.stride(1) != 1:
                     h = h.contiguous()
@@ -155,9 +180,13 @@ def layerwise_inference(model, indptr, indices, feat, batch_rows=65536, device=N
                 W, bias = _layer_params(model, layer)
                 din = W.shape[1] // 2 if sage else W.shape[1]  # (not h.shape[1]: q8 rows are S bytes wide)
                 out = th.empty((n, W.shape[0]), dtype=th.float32 if nn else dtype, device=device)
+                pooled = _pool_rows(layer, h, indptr64, indices64, n, batch_rows, dtype) if pool else None
                 for a in range(0, n, batch_rows):
                     b = min(a + batch_rows, n)
-                    if nn is None:
+                    if pool:
+                        own = models.decode_q8(h[a:b], din) if h.dtype == th.uint8 else h[a:b].to(dtype)
+                        z = th.cat([own, pooled[a:b]], 1)
+                    elif nn is None:
                         z = _chunk_op_by_op(sage, h, indptr64, indices64, a, b, src_factor, dtype)
                     elif sage:
                         z = th.empty((b - a, 2 * din), dtype=th.float32, device=device)

@@ -232,9 +232,10 @@ class FusedSAGEConv(nn.Module):
         bound = 1 / in_feats ** 0.5
         nn.init.uniform_(self.bias, -bound, bound)
 
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        """accepts the op-by-op layout too (fc_self.weight / fc_neigh.weight / fc_neigh.bias: SAGEConvMean here, DGL's
-        SAGEConv in the reference's checkpoints): the two maps side by side are this layer's weight"""
+    @staticmethod
+    def merge_state_dict(state_dict, prefix):
+        """the op-by-op layout's entries (fc_self.weight / fc_neigh.weight / fc_neigh.bias) rewritten in place as this
+        layout's weight and bias: the two maps side by side are the fused layer's weight"""
         ks, kn, kb = prefix + "fc_self.weight", prefix + "fc_neigh.weight", prefix + "fc_neigh.bias"
         ksb = prefix + "fc_self.bias"
         if ks in state_dict and kn in state_dict and prefix + "weight" not in state_dict:
@@ -244,6 +245,10 @@ class FusedSAGEConv(nn.Module):
             parts = [state_dict.pop(k) for k in (kb, ksb) if k in state_dict]
             if parts and prefix + "bias" not in state_dict:
                 state_dict[prefix + "bias"] = parts[0] if len(parts) == 1 else parts[0] + parts[1]
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        """accepts the op-by-op layout too (SAGEConvMean here, DGL's SAGEConv in the reference's checkpoints)"""
+        self.merge_state_dict(state_dict, prefix)
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def split_state_dict(self, prefix=""):
@@ -259,6 +264,108 @@ class FusedSAGEConv(nn.Module):
             return _FusedSageFn.apply(h, self.weight, self.bias, block, num_dst)
         agg = _sum_to_dst(block, h) / _in_degree(block, h.dtype).clamp(min=1).unsqueeze(1)
         return th.cat([h[:num_dst], agg], 1).mm(self.weight.t()) + self.bias
+
+
+def _relu_max_to_dst(block, p):
+    """max_{(u->v)} relu(p_u) per destination, op by op: relu(p)[row] (an E x D tensor) and one scatter amax into zeros
+    (a destination without an edge keeps 0, as DGL fills it)"""
+    row, col = block.row.long(), block.col.long()
+    out = th.zeros((block.number_of_dst_nodes(), p.shape[1]), dtype=p.dtype, device=p.device)
+    return out.scatter_reduce_(0, col.unsqueeze(1).expand(-1, p.shape[1]), F.relu(p)[row], "amax", include_self=True)
+
+
+class SAGEConvPool(nn.Module):
+    """h_dst' = W_self h_dst + W_neigh max_{(u->v)} relu(W_pool h_u + b_pool) + b   (dgl.nn.SAGEConv(..., 'pool')), op by
+    op; the parameters under DGL's names (fc_pool.*, fc_self.weight, fc_neigh.*), as SAGEConvMean maps them"""
+
+    def __init__(self, in_feats, out_feats):
+        super().__init__()
+        self.fc_pool = TallLinear(in_feats, in_feats, bias=True)
+        self.fc_self = TallLinear(in_feats, out_feats, bias=False)
+        self.fc_neigh = TallLinear(in_feats, out_feats, bias=True)
+
+    def forward(self, block, h):
+        num_dst = block.number_of_dst_nodes()
+        return self.fc_self(h[:num_dst]) + self.fc_neigh(_relu_max_to_dst(block, self.fc_pool(h)))
+
+
+class _FusedSagePoolFn(th.autograd.Function):
+    """everything of SAGEConv('pool') behind the pool projection p = W_pool h + b_pool as ONE autograd node: z = [h_dst |
+    max_{(u->v)} relu(p_u)], out = z W^T + b with W = [W_self | W_neigh].  The maxima land straight in the right half of
+    z (fgnn_block_relu_max_forward: ReLU folded in, no relu(p)[row] tensor, no atomic per element); what is kept for the
+    backward pass is the int32 winner table, not p; the gradient of p is one scatter of gz's right half, read in place
+    (fgnn_block_relu_max_backward)."""
+
+    @staticmethod
+    def forward(ctx, h, p, weight, bias, block, num_dst):
+        from fgnn_hip.nn import block_relu_max_into
+        din = weight.shape[1] // 2
+        z = th.empty((num_dst, 2 * din), dtype=th.float32, device=h.device)
+        z[:, :din] = h[:num_dst]
+        arg = th.empty((num_dst, din), dtype=th.int32, device=h.device)
+        block_relu_max_into(z[:, din:], arg, p if p.stride(1) == 1 else p.contiguous(), block.row, block.col)
+        ctx.save_for_backward(z, weight, arg, block.row)
+        ctx.num_src = h.shape[0]
+        return th.addmm(bias, z, weight.t())
+
+    @staticmethod
+    def backward(ctx, gout):
+        from fgnn_hip.nn import block_relu_max_backward_into
+        z, weight, arg, row = ctx.saved_tensors
+        gout = gout.contiguous()
+        num_dst, din = arg.shape
+        gw = _weight_grad(gout, z) if ctx.needs_input_grad[2] else None
+        gb = gout.sum(0) if ctx.needs_input_grad[3] else None
+        gh = gp = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gz = gout.mm(weight)
+            if ctx.needs_input_grad[0]:
+                gh = th.zeros((ctx.num_src, din), dtype=gz.dtype, device=gz.device)
+                gh[:num_dst] = gz[:, :din]
+            if ctx.needs_input_grad[1]:
+                gp = th.zeros((ctx.num_src, din), dtype=gz.dtype, device=gz.device)
+                block_relu_max_backward_into(gp, arg, row, gz[:, din:])
+        return gh, gp, gw, gb, None, None
+
+
+class FusedSAGEPoolConv(nn.Module):
+    """SAGEConvPool with the two output maps as one weight [out, 2 in] = [W_self | W_neigh] and everything behind the
+    pool projection as one autograd node (_FusedSagePoolFn); fc_pool is the same TallLinear under the same name.  Off the
+    GPU / without the HIP library it computes SAGEConvPool's arithmetic op by op.  State dicts load both ways between the
+    two layouts, as FusedSAGEConv's do.  fp16 / q8 input rows: fc_pool is a GEMM and needs every row in fp32, so this
+    layer is NOT among those input_rows hands such rows as they are -- the model upcasts or decodes them once."""
+
+    def __init__(self, in_feats, out_feats):
+        super().__init__()
+        self.in_feats = in_feats
+        self.fc_pool = TallLinear(in_feats, in_feats, bias=True)
+        self.weight = nn.Parameter(th.empty(out_feats, 2 * in_feats))
+        self.bias = nn.Parameter(th.zeros(out_feats))
+        for half in (self.weight[:, :in_feats], self.weight[:, in_feats:]):  # each map initialised like nn.Linear's
+            nn.init.kaiming_uniform_(half, a=5 ** 0.5)
+        bound = 1 / in_feats ** 0.5
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        FusedSAGEConv.merge_state_dict(state_dict, prefix)
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def split_state_dict(self, prefix=""):
+        """this layer's parameters in the op-by-op layout (what SAGEConvPool / DGL's pool SAGEConv load)"""
+        d = self.in_feats
+        return {prefix + "fc_pool.weight": self.fc_pool.weight.detach().clone(),
+                prefix + "fc_pool.bias": self.fc_pool.bias.detach().clone(),
+                prefix + "fc_self.weight": self.weight.detach()[:, :d].clone(),
+                prefix + "fc_neigh.weight": self.weight.detach()[:, d:].clone(),
+                prefix + "fc_neigh.bias": self.bias.detach().clone()}
+
+    def forward(self, block, h):
+        num_dst = block.number_of_dst_nodes()
+        p = self.fc_pool(h)
+        if _fused_layers_apply(block, h):
+            return _FusedSagePoolFn.apply(h, p, self.weight, self.bias, block, num_dst)
+        d = self.in_feats  # SAGEConvPool's two maps, op for op
+        return F.linear(h[:num_dst], self.weight[:, :d]) + F.linear(_relu_max_to_dst(block, p), self.weight[:, d:], self.bias)
 
 
 class GraphConv(nn.Module):
@@ -647,11 +754,16 @@ class GATv2(_AttentionNet):
 
 
 class SAGE(nn.Module):
-    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True):
+    CONVS = {"mean": (SAGEConvMean, FusedSAGEConv), "pool": (SAGEConvPool, FusedSAGEPoolConv)}  # (op by op, fused)
+
+    def __init__(self, in_feats, n_hidden, n_classes, n_layers, dropout, fused=True, aggregator="mean"):
         super().__init__()
         dims = [in_feats] + [n_hidden] * (n_layers - 1) + [n_classes]
+        if aggregator not in self.CONVS:
+            raise ValueError("SAGE aggregator %r: one of %s" % (aggregator, sorted(self.CONVS)))
+        self.aggregator = aggregator
         # fused=False: the op-by-op layer (two nn.Linear-like maps per layer, the layout a DGL SAGEConv checkpoint has)
-        conv = FusedSAGEConv if fused else SAGEConvMean
+        conv = self.CONVS[aggregator][bool(fused)]
         self.layers = nn.ModuleList(conv(dims[i], dims[i + 1]) for i in range(n_layers))
         self.dropout = nn.Dropout(dropout)
         # set by a training loop that uses fgnn_hip.nn.Adam: its device-side step count keys the dropout masks, so

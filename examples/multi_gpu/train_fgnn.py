@@ -33,7 +33,7 @@ from models import MODELS  # noqa: E402
 
 # run-config entries that belong to the script, not to sam.config()
 SCRIPT_KEYS = ("sample_workers", "train_workers", "model", "no_train", "report_acc", "op_by_op", "async_train",
-               "exact_eval")
+               "exact_eval", "aggregator")
 
 
 def build_parser():
@@ -48,6 +48,8 @@ def build_parser():
                     help="--report-acc by exact layer-wise inference over the full graph (examples/inference.py; graphsage, "
                          "gcn and gat) instead of sampled evaluation batches")
     ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
+    ap.add_argument("--aggregator", default="mean", choices=["mean", "pool"],
+                    help="graphsage: mean, or the max-pooling aggregator (DGL's 'pool')")
     ap.add_argument("--sample-type", default=None)
     ap.add_argument("--fanout", nargs="+", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=8000)
@@ -114,7 +116,7 @@ def get_run_config(args):
         rc["train_workers"] = ["cuda:%d" % (ns + i) for i in range(nt)]
     rc.update(model=args.model, num_hidden=args.num_hidden, lr=args.lr, dropout=args.dropout,
               pipeline=not args.no_pipeline, no_train=args.no_train, report_acc=args.report_acc, op_by_op=args.op_by_op,
-              async_train=args.async_train, exact_eval=args.exact_eval)
+              async_train=args.async_train, exact_eval=args.exact_eval, aggregator=args.aggregator)
     return rc
 
 
@@ -158,6 +160,8 @@ def run_train(worker_id, rc):
     sam.train_init(worker_id, ctx)
     num_layer = rc["num_layer"]
     kw = dict(fused=False) if rc["op_by_op"] else {}
+    if rc["model"] == "graphsage":
+        kw["aggregator"] = rc["aggregator"]
     model = MODELS[rc["model"]](sam.feat_dim(), rc["num_hidden"], sam.num_class(), num_layer, rc["dropout"], **kw).to(dev)
     accuracy = None
     if rc["report_acc"] and worker_id == 0 and rc["model"] != "pinsage":
@@ -270,6 +274,8 @@ def main():
         torch.set_num_threads(1)
         torch.manual_seed(0)
         kw = dict(fused=False) if rc["op_by_op"] else {}
+        if rc["model"] == "graphsage":
+            kw["aggregator"] = rc["aggregator"]
         rc["global_cpu_model"] = MODELS[rc["model"]](sam.feat_dim(), rc["num_hidden"], sam.num_class(), rc["num_layer"],
                                                      rc["dropout"], **kw)
         rc["global_cpu_model"].share_memory()

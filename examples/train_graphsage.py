@@ -69,6 +69,8 @@ def main():
                     help="after the last epoch, write the [N, n_classes] logits of every node (exact layer-wise "
                          "inference over the full graph) to FILE.npy")
     ap.add_argument("--op-by-op", action="store_true", help="the op-by-op layers instead of the fused ones")
+    ap.add_argument("--aggregator", default="mean", choices=["mean", "pool"],
+                    help="graphsage: mean, or the max-pooling aggregator (DGL's 'pool')")
     # GAT (example/samgraph/train_gat.py: 8 heads x 32 hidden, attention dropout = feature dropout)
     ap.add_argument("--num-heads", type=int, default=8, help="gat / gatv2: attention heads of the inner layers")
     ap.add_argument("--attn-drop", type=float, default=None, help="gat / gatv2: attention dropout (default: --dropout)")
@@ -124,6 +126,8 @@ def main():
     dev = th.device(trainer_ctx)
     num_layer = args.num_layer if args.model == "pinsage" else len(args.fanout)
     kw = dict(heads=args.num_heads, attn_drop=args.attn_drop) if args.model in ("gat", "gatv2") else {}
+    if args.model == "graphsage":
+        kw["aggregator"] = args.aggregator
     model = MODELS[args.model](sam.feat_dim(), args.num_hidden, sam.num_class(), num_layer, args.dropout,
                                fused=not args.op_by_op, **kw).to(dev)
     get_blocks = sam.get_dgl_blocks_with_weights if args.model == "pinsage" else sam.get_dgl_blocks

@@ -140,6 +140,9 @@ SIGNATURES = {
                                 _P)),
     "fgnn_gatv2_backward": (_I, (_P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P, _Z, _Z, _Z, _Z, _F, _F, _U64, _P, _U32, _P, _Z,
                                  _P, _Z, _P, _P, _Z, _P)),
+    "fgnn_block_relu_max_workspace_bytes": (_Z, (_Z, _Z)),
+    "fgnn_block_relu_max_forward": (_I, (_P, _P, _Z, _P, _Z, _Z, _Z, _P, _Z, _P, _P, _Z, _P)),
+    "fgnn_block_relu_max_backward": (_I, (_P, _P, _Z, _P, _Z, _Z, _Z, _P, _Z, _P)),
     "fgnn_sage_finish_z": (_I, (_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P)),
     "fgnn_sage_finish_z_f16": (_I, (_P, _Z, _P, _Z, _P, _P, _Z, _Z, _P)),
     "fgnn_sage_grad_prep": (_I, (_P, _Z, _P, _P, _P, _Z, _Z, _Z, _P)),

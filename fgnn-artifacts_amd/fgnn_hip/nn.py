@@ -502,6 +502,99 @@ def gatv2_attention(fs, fd, attn, row, col, num_dst, negative_slope=0.2, attn_dr
     return _Gatv2Attention.apply(out, fs, fd, attn, row, col, float(negative_slope), p, int(seed), d_step, int(tag))
 
 
+# ---- GraphSAGE max-pooling aggregator: fused ReLU-max over a block (csrc/block_relu_max.hip) ---------------------------------
+
+_RELU_MAX_WS = {}
+
+
+def block_relu_max_workspace(device, num_dst, dim):
+    """the key table of fgnn_block_relu_max_forward (one 64-bit word per destination and column), cached per (device,
+    sizes) like gat_workspace: call it BEFORE a graph capture whose first block_relu_max call would otherwise allocate it
+    inside the capture.  The call zeroes it itself."""
+    key = (torch.device(device), num_dst, dim)
+    ws = _RELU_MAX_WS.get(key)
+    if ws is None:
+        nbytes = _lib.load().fgnn_block_relu_max_workspace_bytes(num_dst, dim)
+        ws = _RELU_MAX_WS[key] = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.int64, device=device)
+    return ws
+
+
+def _cols_ok(t):
+    """[rows, dim] fp32 with unit stride inside a row (a column block of a wider matrix is fine)"""
+    return t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+
+
+def block_relu_max_into(out, arg, x, row, col):
+    """fgnn_block_relu_max_forward, no autograd: out[v, c] = max(0, max over the edges e with col[e] == v of
+    x[row[e], c]) and arg[v, c] = the smallest such e that attains a positive maximum, else -1.  out [num_dst, dim] (fp32,
+    OVERWRITTEN) and x [num_src, dim] may be column blocks of wider matrices; arg is int32 [num_dst, dim], contiguous."""
+    num_dst, dim = out.shape
+    assert _cols_ok(out) and _cols_ok(x) and x.shape[1] == dim
+    assert arg.dtype == torch.int32 and arg.is_contiguous() and arg.shape == (num_dst, dim)
+    assert row.dtype == torch.int32 and col.dtype == torch.int32 and row.is_contiguous() and col.is_contiguous()
+    assert row.numel() == col.numel()
+    ws = block_relu_max_workspace(x.device, num_dst, dim)
+    _lib._check(_lib.load().fgnn_block_relu_max_forward(_ptr(row), _ptr(col), row.numel(), _ptr(x), x.stride(0), num_dst,
+                                                        dim, _ptr(out), out.stride(0), _ptr(arg), _ptr(ws),
+                                                        ws.numel() * 8, _st(x)), "fgnn_block_relu_max_forward")
+    return out
+
+
+def block_relu_max_backward_into(gx, arg, row, gout):
+    """fgnn_block_relu_max_backward, no autograd: gx[row[arg[v, c]], c] += gout[v, c] wherever arg[v, c] >= 0, into the
+    caller-initialised gx [num_src, dim]; gx and gout [num_dst, dim] may be column blocks of wider matrices"""
+    num_dst, dim = gout.shape
+    assert _cols_ok(gout) and _cols_ok(gx) and gx.shape[1] == dim
+    assert arg.dtype == torch.int32 and arg.is_contiguous() and arg.shape == (num_dst, dim)
+    assert row.dtype == torch.int32 and row.is_contiguous()
+    _lib._check(_lib.load().fgnn_block_relu_max_backward(_ptr(arg), _ptr(row), row.numel(), _ptr(gout), gout.stride(0),
+                                                         num_dst, dim, _ptr(gx), gx.stride(0), _st(gout)),
+                "fgnn_block_relu_max_backward")
+    return gx
+
+
+class _BlockReluMax(torch.autograd.Function):
+    """saves arg and row, not x: the winners are the whole backward information.  `out` is the first input, as
+    _Gatv2Attention's: where it is a view (a column block of z) autograd rebases the view's history on this node"""
+
+    @staticmethod
+    def forward(ctx, out, x, row, col):
+        if not _cols_ok(x):
+            x = x.contiguous()
+        ctx.mark_dirty(out)
+        arg = torch.empty(out.shape, dtype=torch.int32, device=x.device)
+        block_relu_max_into(out, arg, x, row, col)
+        ctx.save_for_backward(arg, row)
+        ctx.num_src = x.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        arg, row = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        if not _cols_ok(gout):
+            gout = gout.contiguous()
+        gx = torch.zeros((ctx.num_src, gout.shape[1]), dtype=torch.float32, device=gout.device)
+        block_relu_max_backward_into(gx, arg, row, gout)
+        return None, gx, None, None
+
+
+def block_relu_max(x, row, col, num_dst, out=None):
+    """max-pooling over a block with the ReLU folded in, as one autograd node differentiable in x:
+        out[v, :] = max(0, max over the edges e with col[e] == v of x[row[e], :])      (no edge: 0)
+    x fp32 [num_src, D], row / col int32 [E].  Returns [num_dst, D]: `out` if given -- an fp32 tensor WITHOUT autograd
+    history that is overwritten, typically a column block of a fused layer's z -- else a new tensor.  The gradient goes
+    to the smallest edge that attains a positive maximum (fgnn_block_relu_max_forward's arg)."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+    assert row.dtype == torch.int32 and col.dtype == torch.int32
+    assert row.is_contiguous() and col.is_contiguous() and row.numel() == col.numel()
+    if out is None:
+        out = torch.empty((num_dst, x.shape[1]), dtype=torch.float32, device=x.device)
+    assert _cols_ok(out) and out.shape == (num_dst, x.shape[1]) and not out.requires_grad
+    return _BlockReluMax.apply(out, x, row, col)
+
+
 # ---- GAT attention over whole CSR rows: exact layer-wise GAT inference (csrc/csr_gat_attention.hip) ---------------------
 
 def csr_gat_max_heads():

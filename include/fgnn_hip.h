@@ -643,6 +643,31 @@ int fgnn_gatv2_backward(const uint32_t *src_index, const uint32_t *dst_index, si
                         uint32_t tag, float *gfs, size_t gfs_ld, float *gfd, size_t gfd_ld, float *gattn, void *ws,
                         size_t ws_bytes, void *stream);
 
+/* ---- GraphSAGE max-pooling aggregator (csrc/block_relu_max.hip; examples/models.py FusedSAGEPoolConv; the layer:
+ * dgl.nn.SAGEConv(..., 'pool')) ------------------------------------------------------------------------------------------
+ * x [num_src, dim] fp32 with row stride x_ld, src_index / dst_index [num_edge], ReLU folded into the maximum:
+ *   m[v,c]   = max over the edges e with dst_index[e] == v of x[src_index[e],c]
+ *   out[v,c] = m[v,c] if m[v,c] > 0 else +0.0                  (a destination without an edge: +0.0)
+ *   arg[v,c] = the smallest e with dst_index[e] == v and x[src_index[e],c] == out[v,c] if out[v,c] > 0, else -1
+ * Inputs are finite; what a NaN does is unspecified.  Every call is stream-ordered: no host synchronisation, no
+ * allocation.  FGNN_EINVAL before any launch: a null required pointer, dim 0, a row stride below dim, a pointer that is
+ * not 4-byte aligned (ws: 8-byte), num_edge >= 2^31 (arg is int32). */
+/* bytes of the forward call's workspace: one 64-bit key per (destination, column) */
+size_t fgnn_block_relu_max_workspace_bytes(size_t num_dst, size_t dim);
+/* out (row stride out_ld >= dim: it may be a column block of a wider matrix, e.g. the right half of [h_dst | max]) and
+ * arg [num_dst, dim] are OVERWRITTEN, for every destination.  Any edge order gives the same out, and arg by the rule
+ * above in that order's own numbering; every x row is read once and nothing of size num_edge x dim is written.  ws:
+ * ws_bytes >= fgnn_block_relu_max_workspace_bytes(num_dst, dim); the call zeroes it itself and expects nothing of its
+ * contents.  num_edge == 0: out all +0.0, arg all -1.  num_dst == 0 returns FGNN_OK and touches nothing. */
+int fgnn_block_relu_max_forward(const uint32_t *src_index, const uint32_t *dst_index, size_t num_edge, const float *x,
+                                size_t x_ld, size_t num_dst, size_t dim, float *out, size_t out_ld, int32_t *arg,
+                                void *ws, size_t ws_bytes, void *stream);
+/* gx[src_index[arg[v,c]], c] += gout[v,c] wherever arg[v,c] >= 0 (an arg >= num_edge adds nothing).  gx (row stride
+ * gx_ld) is fp32 and caller-initialised, gout has the row stride gout_ld; one float atomic per live element, so an
+ * element of gx stays within (k + 8) 2^-23 of the sum of the magnitudes of its k terms. */
+int fgnn_block_relu_max_backward(const int32_t *arg, const uint32_t *src_index, size_t num_edge, const float *gout,
+                                 size_t gout_ld, size_t num_dst, size_t dim, float *gx, size_t gx_ld, void *stream);
+
 /* ---- fused pieces of a GraphSAGE training step (consumer side, csrc/train_ops.hip) ----------------------------------
  * Elementwise work a training step otherwise does with two to four framework ops each; one launch apiece because the
  * step is replayed as a captured HIP graph, where every node costs the GPU 15-20 us whatever it does.  fp32, the same

@@ -19,6 +19,9 @@ from models import MODELS, SAGE  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--model", default="graphsage", choices=list(MODELS))
+ap.add_argument("--aggregator", default="mean", choices=["mean", "pool"],
+                help="graphsage: pool = the max-pooling layers, A/B'd like gcn / pinsage on the products batch, then the "
+                     "forward kernel alone against the sum kernel on the same block and width")
 ap.add_argument("--fused", type=int, default=None, choices=[0, 1],
                 help="the fused layers (1) or the op-by-op ones (0); default 1 (graphsage: SAGE_FUSED)")
 ap.add_argument("--ab", type=int, default=5, help="gcn / pinsage: alternations of the op-by-op and the fused model")
@@ -78,7 +81,9 @@ def ab_main():
     from fgnn_hip.nn import Adam, softmax_xent
     dev = "cuda:0"
     torch.cuda.set_device(0)
-    workload = args.workload or {"gcn": "twitter", "pinsage": "uk-2006-05", "gat": "products", "gatv2": "products"}[args.model]
+    workload = args.workload or {"gcn": "twitter", "pinsage": "uk-2006-05", "gat": "products", "gatv2": "products",
+                                 "graphsage": "products"}[args.model]
+    kw = dict(aggregator=args.aggregator) if args.model == "graphsage" else {}
     blocks, w = real_batch_blocks(workload, dev)
     print("%s batch of %s: %s" % (args.model, workload, ", ".join(
         "%d src -> %d dst, %d edges" % (b.nsrc, b.ndst, b.row.numel()) for b in blocks)))
@@ -88,7 +93,7 @@ def ab_main():
     steppers = {}
     for fused in (0, 1):
         torch.manual_seed(0)
-        model = MODELS[args.model](w["feat_dim"], 256, w["num_class"], len(blocks), 0.5, fused=bool(fused)).to(dev)
+        model = MODELS[args.model](w["feat_dim"], 256, w["num_class"], len(blocks), 0.5, fused=bool(fused), **kw).to(dev)
         opt = Adam(model.parameters(), lr=0.003)
         model.dropout_step = opt.step_count
 
@@ -129,6 +134,36 @@ def ab_main():
     print("per-kernel times of 5 steps, fused=%d" % which)
     print(prof.key_averages().table(sort_by="self_cuda_time_total", row_limit=int(os.environ.get('ROWS', '30')),
                                     max_name_column_width=70))
+    if kw.get("aggregator") == "pool":
+        pool_kernel_ab(blocks[1], 256, run)
+
+
+def pool_kernel_ab(b, dim, run):
+    """fgnn_block_relu_max_forward (zero fill, edge pass with 64-bit atomics, unpack) against fgnn_block_aggregate_ex
+    (the sum) on the same block and width: ms per call and the rate of the bytes either must move at the least -- E
+    rows read, the output written, and for the maximum the winner table and the key table written, updated and read"""
+    import statistics
+    from fgnn_hip.nn import aggregate_into, block_relu_max_into, block_relu_max_workspace
+    E = b.row.numel()
+    x = torch.randn(b.nsrc, dim, device=b.row.device)
+    out, arg = torch.zeros((b.ndst, dim), device=x.device), torch.empty((b.ndst, dim), dtype=torch.int32, device=x.device)
+    block_relu_max_workspace(x.device, b.ndst, dim)
+    fns = {"relu_max": lambda: block_relu_max_into(out, arg, x, b.row, b.col),
+           "sum": lambda: aggregate_into(out, x, b.row, b.col)}
+    nbytes = {"relu_max": 4 * dim * (E + 2 * b.ndst) + 8 * E + 8 * dim * b.ndst * 3, "sum": 4 * dim * (E + b.ndst) + 8 * E}
+    ms = {k: [] for k in fns}
+    for k in fns:
+        run(fns[k], 20)
+    for _ in range(args.ab):
+        for k in fns:
+            ms[k].append(run(fns[k], args.ab_steps))
+    print("forward kernels on %d src -> %d dst, %d edges, %d columns" % (b.nsrc, b.ndst, E, dim))
+    for k, v in ms.items():
+        med = statistics.median(v)
+        print("%s: median %.4f ms, min %.4f, max %.4f, spread %.4f; %.1f MB -> %.0f GB/s"
+              % (k, med, min(v), max(v), max(v) - min(v), nbytes[k] * 1e-6, nbytes[k] / med * 1e-6))
+    print("not written by the fused layer: relu(p)[row], %d x %d fp32 = %.1f MB, forward and again backward"
+          % (E, dim, 4e-6 * E * dim))
 
 
 class Block:
@@ -210,7 +245,7 @@ def feat_store_main():
 if args.feat_store == "f16":
     feat_store_main()
     sys.exit(0)
-if args.model != "graphsage":
+if args.model != "graphsage" or args.aggregator == "pool":
     ab_main()
     sys.exit(0)
 
